@@ -15,26 +15,43 @@ synthetic trace. For N>1 the default is SURVEY config C3: each rank owns
 data-path collective); the per-tick statistics are reduced on the device and
 summed across GPUs with RCCL on a side stream inside the engine.
 
-Also in the same line (N=1, default workload):
+A plain run does only what the headline needs: it sets the engine up, runs
+the warm-up ticks, times the steps, writes its outputs if --dump-outputs is
+given and prints the result line (`value`, `ms_per_step`, the statistics
+check of the timed ticks, and the roofline's wall-clock fields).
+
+With --full the line also carries the lean kernel's own duration and the
+roofline fields derived from it (untimed profile passes), the stream probe,
+the CPU baseline with its oracle slice check, the median of --repeats timed
+regions (default 5 there) and, at N=1 with the default workload:
   * `fused`: the same workload with up to 16 steady ticks per launch of
     tick_fused_kernel (ticks_per_launch = 16; state kept in registers between
     the ticks of a launch — NOT the §8(d) form, so never in `value` or
     `roofline`), with its own kernel fraction;
   * `extra_workloads`: SURVEY configs C4 (2^22 x 7 replicas, leader-isolation
     churn, RAFT semantics) and C5 (E=64 with CRC32C), each timed with the same
-    protocol, with its own roofline and statistics check.
+    protocol (at most EXTRA_MAX_STEPS ticks per region, whatever --steps is),
+    with its own roofline and statistics check.
+The CPU baseline's oracle sample follows the engine through every tick it
+ran; for a long run it takes fewer groups, so that its work stays bounded.
 
 Protocol: W untimed warm-up ticks, then the timed region of
-exactly K ticks (barrier + synchronize on both sides, max over ranks) is
-repeated --repeats times (default 5) and the median is reported. The
-roofline's `achieved` uses the dominant kernel's own average duration,
-measured by HIP events attached to its dispatches on the engine stream
-(profile mode 1) in a separate, untimed pass of K ticks: for the steady
-lines one pair spanning the call's back-to-back launches (so it matches a
-rocprofv3 kernel trace of the timed call), for the churn lines a pair on
-every dispatch of the lean kernel.
+exactly K ticks (barrier + synchronize on both sides, max over ranks). A
+plain run times one region, so --steps is the number of timed ticks of the
+run; with --repeats R (default 5 under --full) the region is repeated and the
+median is reported. With --full the roofline's `achieved` uses the dominant
+kernel's own average duration, measured by HIP events attached to its
+dispatches on the engine stream (profile mode 1) in a separate, untimed pass
+of K ticks: for the steady lines one pair spanning the call's back-to-back
+launches (so it matches a rocprofv3 kernel trace of the timed call), for the
+churn lines a pair on every dispatch of the lean kernel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C4R|C4REF|C5]
+--dump-outputs DIR writes, after the timed ticks and before anything else
+touches the engine, what the last timed call returned and left behind as
+DIR/<name>.npy in float64 (dump_outputs below). The trace and the staged
+values are seeded, so two runs with the same arguments dump the same arrays.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C4R|C4REF|C5] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -192,6 +209,11 @@ WORKLOADS["C5V"] = dict(WORKLOADS["C5"], corrupt=300, ring_depth=512,
                         desc=WORKLOADS["C5"]["desc"] + ", EXT corruption 300/65536 per follower and tick (rejections "
                                                        "timed)")
 EXTRA_DEFAULT = ("C2X", "C4", "C5", "C2S", "C4S", "C5V")
+# An extra workload is timed over at most this many ticks per region, whatever
+# --steps the headline is given: a staged line holds steps x E x G int64 values
+# on the host and in HBM (C4S: 32 MB per tick), and --full has to end in minutes
+# (each extra line reports the `steps` it ran).
+EXTRA_MAX_STEPS = 64
 
 
 def _sm64_np(x):
@@ -247,6 +269,12 @@ def cpu_baseline(wl, R, E, K, crc, groups, ticks, leader=0, check=None):
         G, T = max(1024, 4 * G // E), max(16, T // 4)
     Geng = wl["groups"] if check is None else len(check[0])
     G = min(G, Geng)
+    if check is not None:
+        # the sample follows the engine to its last tick, however many --steps ran:
+        # fewer groups for a longer span, so that groups x ticks stays what was asked for
+        span = check[1] - (wl["settle"] if wl.get("init") == "new" else 1)
+        if span > T:
+            G = max(min(G, 256), G * T // span)
     # a seeded, unaligned offset inside the engine's group range
     off = 0 if G >= Geng else int(np.random.default_rng(wl["seed"]).integers(0, Geng - G + 1))
     staged = bool(wl.get("staged"))
@@ -351,6 +379,44 @@ def median(xs):
     return xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2])
 
 
+DUMP_DIGESTS = 1 << 20        # groups whose state digest is dumped (16 MB as two float64 halves)
+DUMP_LOG_ENTRIES = 1 << 19    # ring entries (groups x R x K) of the dumped state slice (<= 16 MB as float64)
+
+
+def _halves(a):
+    """64-bit integers as [..., 2] float64 (high and low 32 bits, each exact)."""
+    u = np.asarray(a).astype(np.uint64)
+    return np.stack([u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)], axis=-1).astype(np.float64)
+
+
+def dump_outputs(path, eng, wl, stats, steps, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, as float64 .npy files under `path` (well under 64 MB in all):
+      stats            raft_tick's statistics of the last timed call (summed over its ticks)
+      last_step_stats  the last tick's own record (raft_tick_records)
+      digest_groups    the local ids of a seeded sample of DUMP_DIGESTS groups (every group if there are fewer)
+      state_digest     their per-group digests of the canonical state (raft_state_digest), [n, 2] halves
+      slice_groups     [first, count) of a seeded slice of groups whose whole canonical state follows
+      state_<field>    raft_store_state_range of that slice, every field (log_value as [..., 2] halves)
+    Everything comes from the engine through the C-ABI; nothing is recomputed here."""
+    os.makedirs(path, exist_ok=True)
+    G, R, K = eng.cfg.groups, eng.cfg.replicas, eng.cfg.ring_depth
+    rng = np.random.default_rng(wl["seed"])
+    out = {"stats": np.asarray(stats, np.float64),
+           "last_step_stats": eng.tick_records(steps)[-1].astype(np.float64)}
+    ids = np.arange(G) if G <= DUMP_DIGESTS else np.sort(rng.choice(G, DUMP_DIGESTS, replace=False))
+    out["digest_groups"] = ids.astype(np.float64)
+    out["state_digest"] = _halves(eng.state_digest()[0][ids])
+    n = max(1, min(G, DUMP_LOG_ENTRIES // (R * K)))
+    first = int(rng.integers(0, G - n + 1))
+    out["slice_groups"] = np.array([first, n], np.float64)
+    for k, a in eng.store_state_range(first, n).items():
+        out["state_" + k] = _halves(a) if a.dtype.itemsize == 8 else a.astype(np.float64)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    for k, a in out.items():
+        np.save(os.path.join(path, k + sfx + ".npy"), a)
+
+
 class Ctx:
     """Process / rank context of one bench run."""
 
@@ -369,11 +435,14 @@ class Ctx:
         torch.cuda.synchronize()
 
 
-def measure(ctx, wl_key, wl, G, R, E, K, steps, warmup, repeats, tpl=1, leader=0, cpu=None, list_count=True):
+def measure(ctx, wl_key, wl, G, R, E, K, steps, warmup, repeats, tpl=1, leader=0, cpu=None, list_count=True,
+            full=True, dump=None):
     """One line: `repeats` timed regions of exactly `steps` ticks of workload
-    `wl` on this rank's shard (G groups) with `tpl` ticks per launch, then the
-    untimed profile passes for the dominant kernel's duration. Returns the
-    line's fields (value over all ranks)."""
+    `wl` on this rank's shard (G groups) with `tpl` ticks per launch, then
+    (dump) the outputs of the last region and (full) the untimed passes: the
+    PCIe-inclusive call of a staged line, the profile passes for the dominant
+    kernel's duration, the stream probe. Returns the line's fields (value
+    over all ranks)."""
     from raftstep import Engine, STAT_NAMES
     from raftstep import dist as rdist
     world, dist = ctx.world, ctx.dist
@@ -436,11 +505,13 @@ def measure(ctx, wl_key, wl, G, R, E, K, steps, warmup, repeats, tpl=1, leader=0
         times.append(el)
         stats += s
         tick += steps
-    # untimed passes: the steady-state kernel's own duration (events attached
-    # to each of its dispatches), then the list kernel's and its group-steps
+    if dump:   # (untimed host reads) what the last timed call returned and left in the engine
+        dump_outputs(dump, eng, wl, s, steps, ctx.rank, world)
+    # untimed passes (--full): the steady-state kernel's own duration (events
+    # attached to each of its dispatches), then the list kernel's and its group-steps
     two_pass = os.environ.get("RAFTSTEP_TWO_PASS", "1") != "0"
     pcie = None
-    if staged:
+    if staged and full:
         # the same call with the values crossing PCIe inside the timed span
         # (raft_stage_values from host memory, then the ticks): never `value`
         vals = staged_values(wl["seed"], base, G, tick, steps, E)
@@ -457,13 +528,15 @@ def measure(ctx, wl_key, wl, G, R, E, K, steps, warmup, repeats, tpl=1, leader=0
                 "what": "raft_stage_values (host buffer -> HBM, %d MB) + the %d ticks, one call, wall clock"
                         % (vals.nbytes // 1000000, steps)}
         del vals
-    eng.profile(1)
-    stage(tick, steps)
-    eng.tick(tick, steps, stats=False)
-    tick += steps
-    kernel_ms, kernel_ticks = eng.profile_read()
+    kernel_ms = kernel_ticks = 0
+    if full:
+        eng.profile(1)
+        stage(tick, steps)
+        eng.tick(tick, steps, stats=False)
+        tick += steps
+        kernel_ms, kernel_ticks = eng.profile_read()
     list_ms = list_launches = list_steps = 0
-    if two_pass and churn:   # the second pass (list kernel over the groups the lean kernel passed on)
+    if full and two_pass and churn:   # the second pass (list kernel over the groups the lean kernel passed on)
         eng.profile(3)
         stage(tick, steps)
         eng.tick(tick, steps, stats=False)
@@ -524,19 +597,18 @@ def measure(ctx, wl_key, wl, G, R, E, K, steps, warmup, repeats, tpl=1, leader=0
                    shared=shared, staged=staged) if two_pass else \
         algorithmic_bytes(R, E, crc) + (8 * E if staged else 0)
     kname = ("tick_fused_kernel" if fused else "tick_lean_kernel") if two_pass else "tick_fast_kernel"
-    avg_kernel_s = kernel_ms / 1e3 / max(kernel_ticks, 1)   # per tick
+    avg_kernel_s = kernel_ms / 1e3 / max(kernel_ticks, 1) if full else None   # per tick
     # C4REF: the lean kernel's algorithmic bytes are those of the live groups it
     # takes (a frozen group is read as 2 B of gmeta and skipped)
     units = G if live_value is None else live_value * elapsed / world / steps
-    achieved = B * units / avg_kernel_s / 1e9
+    achieved = B * units / avg_kernel_s / 1e9 if full else None
     workload = f"{wl_key}: {G} x {R}-replica groups per GPU, {wl['desc']}, E={E}, K={K}"
     pmc, pmc_src = load_pmc(workload, kname, mean_tpl)
     # per tick (a steady tick is two launches over the halves of the groups)
     traffic = (pmc.get("hbm_bytes_per_tick") or pmc["hbm_bytes_per_launch"]) / mean_tpl if pmc else None
     B_survey = algorithmic_bytes(R, E, crc)
-    roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_scope": TRAFFIC_SCOPE,
-            "frac_measured": (traffic / avg_kernel_s / 1e9 / HBM_PEAK_GBS) if traffic else None,
+    roof = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "traffic": traffic, "traffic_scope": TRAFFIC_SCOPE,
             "traffic_source": pmc_src,
             "kernel": kname,
             "ticks_per_launch": mean_tpl,
@@ -553,18 +625,21 @@ def measure(ctx, wl_key, wl, G, R, E, K, steps, warmup, repeats, tpl=1, leader=0
                   if shared else "")) if two_pass else
                 "SURVEY.md §8(d) B(R,E), per-replica SoA"),
             "units_per_launch": units * (mean_tpl if fused else 1),
-            "avg_kernel_us": avg_kernel_s * 1e6 * (mean_tpl if fused else 1),
-            "avg_kernel_us_per_tick": avg_kernel_s * 1e6,
             # the same bytes over the timed region's wall clock (host launch
             # and readback included): a profiler-free lower bound of `achieved`
             "achieved_wall": B * value / world / 1e9,
             "frac_wall": B * value / world / 1e9 / HBM_PEAK_GBS,
-            "kernel_launches": kernel_ticks if not fused else -(-kernel_ticks // tpl),
             # SURVEY §8(d)'s per-replica SoA figure at the measured tick rate:
             # the bandwidth an uncompressed SoA engine would need for this
             # throughput (above the HBM peak = beyond any per-replica layout)
             "survey_bytes_per_group_step": B_survey,
             "survey_equivalent_GBs": B_survey * value / world / 1e9}
+    if full:   # the fields that need the kernel's own duration (the untimed profile pass)
+        roof.update({"achieved": achieved, "frac": achieved / HBM_PEAK_GBS,
+                     "frac_measured": (traffic / avg_kernel_s / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                     "avg_kernel_us": avg_kernel_s * 1e6 * (mean_tpl if fused else 1),
+                     "avg_kernel_us_per_tick": avg_kernel_s * 1e6,
+                     "kernel_launches": kernel_ticks if not fused else -(-kernel_ticks // tpl)})
     line = {
         "value": value, "ms_per_step": elapsed * 1e3 / steps, "steps": steps, "warmup": warmup,
         "workload": workload, "groups_per_gpu": G, "groups_total": G * world, "replicas": R,
@@ -591,7 +666,7 @@ def measure(ctx, wl_key, wl, G, R, E, K, steps, warmup, repeats, tpl=1, leader=0
                     "copy carries the stamp itself; a corrupted copy -- its last value's bit 0 flipped -- is "
                     "recomputed and rejected: AppendEntries false, main.go:148-149 append skipped); rejections = "
                     "AppendEntries answered false in the timed region"}
-    if two_pass and churn:
+    if full and two_pass and churn:
         # the list kernel: the full fast-path body over the groups the lean
         # kernel passed on (elections, first rounds, returns, isolated
         # leaders), two steps per launch in the pipelined tick, priced with
@@ -618,8 +693,10 @@ def measure(ctx, wl_key, wl, G, R, E, K, steps, warmup, repeats, tpl=1, leader=0
     # this rank's own numbers (multi_gpu.per_rank: where scaling is lost)
     line["rank_local"] = {"ms_per_step": median(local_times) * 1e3 / steps,
                           "repeat_ms_per_step": [x * 1e3 / steps for x in local_times],
-                          "lean_kernel_us_per_tick": avg_kernel_s * 1e6, "stat_allreduces": allreduces}
-    if world == 1 and not churn and not crc and E == 1 and not fused and hasattr(eng.lib, "raft_stream_probe"):
+                          "lean_kernel_us_per_tick": avg_kernel_s * 1e6 if full else None,
+                          "stat_allreduces": allreduces}
+    if full and world == 1 and not churn and not crc and E == 1 and not fused and \
+            hasattr(eng.lib, "raft_stream_probe"):
         # this device's sustained rate for the lean kernel's byte mix and access
         # shape at the same size (raft_stream_probe: fresh buffers, no Raft
         # state): the practical roofline of this kernel on this box
@@ -650,7 +727,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps ticks; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps ticks; the median is reported (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: kernel durations and roofline fractions (untimed profile "
+                         "passes), stream probe, CPU baseline and oracle slice check, the `fused` block, the extra "
+                         "workloads (at most %d ticks per timed region each), PCIe-inclusive lines (narrowed by "
+                         "--no-cpu-baseline, --no-fused, --extra, --no-list-count, which mean nothing without it)"
+                         % EXTRA_MAX_STEPS)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed call returned and left in the engine as DIR/<name>.npy "
+                         "(float64; dump_outputs). Its host reads come after the timed ticks; like any host read "
+                         "they copy shared entries back into the replica rings, so under --full the untimed "
+                         "passes that follow start from that form")
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: C2 at --gpus 1, C3 (2^21 groups per GPU) at --gpus > 1")
     ap.add_argument("--groups-per-gpu", type=int, default=None)
@@ -714,9 +803,11 @@ def main():
     G = args.groups_per_gpu or wl["groups"]
     E = args.entries or wl["entries"]
     K = args.ring_depth or wl["ring_depth"]
-    cpu = None if args.no_cpu_baseline else (args.cpu_groups, args.cpu_ticks)
-    head = measure(ctx, wl_key, wl, G, R, E, K, args.steps, args.warmup, args.repeats, tpl=1, leader=args.leader,
-                   cpu=cpu, list_count=not args.no_list_count)
+    full = args.full
+    repeats = args.repeats or (5 if full else 1)
+    cpu = None if (args.no_cpu_baseline or not full) else (args.cpu_groups, args.cpu_ticks)
+    head = measure(ctx, wl_key, wl, G, R, E, K, args.steps, args.warmup, repeats, tpl=1, leader=args.leader,
+                   cpu=cpu, list_count=not args.no_list_count, full=full, dump=args.dump_outputs)
     ok = head["stats_check"]
 
     multi = None
@@ -742,8 +833,8 @@ def main():
     steady_default = args.workload is None and world == 1 and not any(
         x is not None for x in (args.groups_per_gpu, args.replicas, args.entries, args.ring_depth))
     fused = None
-    if world == 1 and not args.no_fused and wl.get("init") != "new" and not wl["crc"]:
-        fl = measure(ctx, wl_key, wl, G, R, E, K, args.steps, args.warmup, args.repeats, tpl=FUSED_TICKS,
+    if full and world == 1 and not args.no_fused and wl.get("init") != "new" and not wl["crc"]:
+        fl = measure(ctx, wl_key, wl, G, R, E, K, args.steps, args.warmup, repeats, tpl=FUSED_TICKS,
                      leader=args.leader)
         ok = ok and fl["stats_check"]
         fused = {"note": "NOT the headline: up to %d steady ticks per launch of tick_fused_kernel, state kept in "
@@ -756,7 +847,7 @@ def main():
     extras = {}
     names = EXTRA_DEFAULT if (args.extra is None and steady_default) else \
         tuple(x for x in (args.extra or "").split(",") if x and x != "none")
-    if world > 1:
+    if world > 1 or not full:
         names = ()
     for name in names:
         if time.perf_counter() - t_start > args.extra_budget:
@@ -764,7 +855,8 @@ def main():
             continue
         xw = WORKLOADS[name]
         xR, xE, xK = xw.get("replicas", R_DEFAULT), xw["entries"], xw["ring_depth"]
-        x = measure(ctx, name, xw, xw["groups"], xR, xE, xK, args.steps, args.warmup, args.repeats, tpl=1,
+        x = measure(ctx, name, xw, xw["groups"], xR, xE, xK, min(args.steps, EXTRA_MAX_STEPS),
+                    min(args.warmup, EXTRA_MAX_STEPS), repeats, tpl=1,
                     cpu=None if args.no_cpu_baseline else (args.cpu_groups // 4, args.cpu_ticks // 4),
                     list_count=not args.no_list_count)
         ok = ok and x["stats_check"]
@@ -794,7 +886,10 @@ def main():
         "roofline": head["roofline"],
         "stats": head["stats"],
         "stats_check": bool(ok),
+        "full": full,
     }
+    if args.dump_outputs:
+        result["outputs_dumped"] = args.dump_outputs
     for k in ("list_kernel", "faults_prefix"):
         if k in head:
             result[k] = head[k]
@@ -823,8 +918,8 @@ def main():
     # flat copies of the nested numbers a reader of the driver's record needs
     # (the driver's `parsed` keeps top-level scalars only)
     r0 = result["roofline"]
-    flat = {"roofline_frac": r0["frac"], "roofline_achieved_GBs": r0["achieved"],
-            "lean_kernel_us_per_tick": r0["avg_kernel_us_per_tick"],
+    flat = {"roofline_frac": r0.get("frac"), "roofline_achieved_GBs": r0.get("achieved"),
+            "lean_kernel_us_per_tick": r0.get("avg_kernel_us_per_tick"),
             "stream_probe_GBs": (r0.get("stream_probe") or {}).get("GBs"),
             "frac_of_stream_probe": r0.get("frac_of_stream_probe"),
             "l3_proof_frac": (r0.get("l3_proof") or {}).get("frac"),

@@ -68,6 +68,34 @@ def test_survey_bytes():
     assert bench.algorithmic_bytes(5, 64, crc=True) == 5293
 
 
+def test_cpu_leg_takes_fewer_groups_for_a_longer_run():
+    """The oracle sample follows the engine to its last tick; when that is
+    further than the ticks asked for, the sample shrinks (groups x ticks
+    stays bounded, down to 256 groups) and the slice check still holds."""
+    import oracle
+    wl = dict(bench.WORKLOADS["C2"], groups=3000)
+    kw = bench.engine_kwargs(wl, 5, 3000, 0, wl["ring_depth"], 1, 0)
+    full = oracle.Oracle(**kw)
+    full.init_steady(0, 0)
+    full.tick(1, 40)
+    dig, _ = full.state_digest()
+    full.close()
+    for ticks, width in ((64, 1200), (20, 600), (4, 256)):
+        sc = bench.cpu_baseline(wl, 5, 1, wl["ring_depth"], 0, 1200, ticks, check=(dig, 41))["oracle_slice_check"]
+        assert sc["ok"] and sc["groups"][1] - sc["groups"][0] == width == sc["digests_equal"], sc
+
+
+def test_dumped_64_bit_words_survive_float64():
+    """--dump-outputs stores 64-bit words (digests, log values) as two float64
+    halves of 32 bits each: exact for every bit pattern, which one float64
+    (53 bits of mantissa) is not."""
+    w = np.array([0, 1, (1 << 53) + 1, (1 << 63) - 1, (1 << 64) - 1, 0x9E3779B97F4A7C15], np.uint64)
+    h = bench._halves(w)
+    assert h.dtype == np.float64 and h.shape == (6, 2)
+    assert np.array_equal((h[:, 0].astype(np.uint64) << np.uint64(32)) | h[:, 1].astype(np.uint64), w)
+    assert np.array_equal(bench._halves(w.view(np.int64)), h)   # signed log values: the same bits
+
+
 @pytest.mark.parametrize("name", ["C2", "C4"])
 def test_cpu_leg_oracle_slice_check(name):
     """the CPU-baseline leg runs its oracle sample over a slice

@@ -10,7 +10,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=gpurun_out/${OUTDIR:-r4ab}
 mkdir -p "$OUT"
-B="python3 -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fused --extra none"
+B="python3 -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fused --extra none"
 # a variant is NAME (the library ablib/NAME, "base" = the tree's) or
 # LABEL+VAR=VAL[+VAR=VAL...] (the tree's library with those environment knobs)
 variant() {   # sets label, lib, envs

@@ -11,7 +11,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
     (cd ablib/r2tree && timeout -k 10 300 python3 -u bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline) \
       > "$OUT/r2_${w}_$r.json" 2> "$OUT/r2_${w}_$r.err" || exit 1
     echo "== $(date +%T) round $r $w cur" >> "$OUT/progress.log"
-    timeout -k 10 300 python3 -u bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-fused --extra none \
+    timeout -k 10 300 python3 -u bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-fused --extra none \
       > "$OUT/cur_${w}_$r.json" 2> "$OUT/cur_${w}_$r.err" || exit 1
   done
 done

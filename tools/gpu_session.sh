@@ -23,8 +23,8 @@ export TMPDIR=/tmp
 [ -n "$LIB" ] && export RAFTSTEP_LIB="$LIB"
 OUT=gpurun_out/${OUTDIR:-r5}
 mkdir -p "$OUT"
-B="python3 -u bench.py --steps 20 --warmup 5"
-Q="--steps 20 --warmup 5 --repeats 1 --no-cpu-baseline --no-fused --extra none --no-list-count"
+B="python3 -u bench.py --full --steps 20 --warmup 5"
+Q="--full --steps 20 --warmup 5 --repeats 1 --no-cpu-baseline --no-fused --extra none --no-list-count"
 P="timeout -s KILL 120 rocprofv3"
 log() { echo "== $(date +%T) $*" >> "$OUT/progress.log"; }
 n=0

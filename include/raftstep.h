@@ -411,7 +411,9 @@ enum raft_diag_counter {
   /* host counters since the last read */
   RAFT_DIAG_TICKS = 64,
   RAFT_DIAG_TICKS_LIST_SKIPPED = 65,  /* ticks run by the lean kernel alone (steady-state list skip) */
-  RAFT_DIAG_GENERAL_LAUNCHES = 66
+  RAFT_DIAG_GENERAL_LAUNCHES = 66,
+  RAFT_DIAG_TICKS_STEADY_FORM = 67    /* ... of those, ticks the lean kernel ran in its steady form (every live group
+                                         proven in the global ring phase; RAFTSTEP_STEADY_FORM=0: never) */
 };
 int raft_diag_enable(raft_engine* e, int on);
 int raft_diag_read(raft_engine* e, uint64_t* counters, uint32_t n);

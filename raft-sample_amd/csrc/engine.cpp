@@ -234,6 +234,20 @@ struct raft_engine {
   bool steady_origin = false;
   bool steady_ok = false;
   bool skipped_list = false;    // the current call skipped the list kernel
+  // Steady form of the lean kernel (tick_steady.hpp). A list-skipping tick
+  // (one tick per launch, no device counters, no timing diagnostics) runs it
+  // while every live group is known to append in the global ring phase:
+  // init_steady puts entry 1 there for a call at tick0 + 1 (k_init.hip), and
+  // consecutive calls keep it there. phase_ok is set by init_steady and
+  // dropped for good by a call that does not start where the last one ended
+  // (after a gap groups drift: the general body writes their own segments
+  // and switches ring segments), a failed call, a state replacement, a host
+  // mutation or poisoning; only the next init_steady sets it again.
+  // RAFTSTEP_STEADY_FORM=0: the general body everywhere (exact either way:
+  // tests/test_gpu_steady_form.py).
+  int steady_form = 1;
+  bool phase_ok = false, phase_done = false;   // (phase_done: the last call issued everything)
+  int64_t phase_next = 0;       // the tick the next call must start at
   // A skipping call without statistics ends with the check record written to
   // tstat[hist_cap + 1] and copied to the pinned buffer (event chk_ev); the
   // next call on the engine waits for it and verifies that nothing was passed
@@ -247,7 +261,7 @@ struct raft_engine {
   // diagnostics: lane class counters on the device (raft_diag_enable), host counters
   int diag_print = 0;
   unsigned long long* dbg_buf = nullptr;   // the device counters (P.dbg while counting)           // RAFTSTEP_DEBUG_FAST: print the class counters after every call (synchronising)
-  uint64_t n_ticks = 0, n_skip_ticks = 0, n_general = 0;
+  uint64_t n_ticks = 0, n_skip_ticks = 0, n_general = 0, n_steady_ticks = 0;
   // handler-batch staging
   void* stage = nullptr;
   size_t stage_cap = 0;
@@ -377,7 +391,7 @@ int settle_check(raft_engine* e) {
       e->poison_msg = "steady-state list skip: " + std::to_string(c[CHK_LISTED]) +
                       " groups were passed to a list kernel that did not run (ticks lost)";
     }
-    if (e->poisoned) e->steady_ok = false;
+    if (e->poisoned) e->steady_ok = e->phase_ok = false;
   }
   if (e->poisoned)
     return fail(RAFT_EINTERNAL, "%s; the engine state is invalid until init_*, load_state or a checkpoint load",
@@ -388,7 +402,7 @@ int settle_check(raft_engine* e) {
 // A call that replaces the state starts by dropping the list-skip proof (the
 // conservative direction, whatever happens next) ...
 void state_replacing(raft_engine* e) {
-  e->steady_origin = e->steady_ok = false;
+  e->steady_origin = e->steady_ok = e->phase_ok = false;
   e->vx_live = false;   // (the state is being replaced: no suffix survives)
   e->sh_live = false;   // (nor a shared entry: every rotation is rewritten)
   e->run_valid = false;
@@ -410,7 +424,7 @@ int vx_flush(raft_engine* e) {
   if (!e->vx_live) return RAFT_OK;
   if (e->vx_tick < 0) {
     e->poisoned = true;
-    e->steady_ok = false;
+    e->steady_ok = e->phase_ok = false;
     e->poison_msg = "a failed raft_tick call left virtual log suffixes undefined (state must be replaced)";
     return fail(RAFT_EINTERNAL, "%s", e->poison_msg.c_str());
   }
@@ -431,7 +445,7 @@ int vx_flush(raft_engine* e) {
 int sh_heartbeat(raft_engine* e) {
   if (!e->sh_done) {
     e->poisoned = true;
-    e->steady_ok = false;
+    e->steady_ok = e->phase_ok = false;
     e->poison_msg = "a failed raft_tick call left shared entries' heartbeat times undefined (state must be replaced)";
     return fail(RAFT_EINTERNAL, "%s", e->poison_msg.c_str());
   }
@@ -749,6 +763,7 @@ int raft_engine_create(const raft_config* cfg, raft_engine** out) {
   if (const char* tp = getenv("RAFTSTEP_TWO_PASS")) e->two_pass = atoi(tp) != 0;
   e->P.diag = diag_lean;
   if (const char* sp = getenv("RAFTSTEP_SPLIT_STEADY")) e->split_steady = atoi(sp) != 0;
+  if (const char* sf = getenv("RAFTSTEP_STEADY_FORM")) e->steady_form = atoi(sf) != 0;
 
   // (the depths the oracle tests cover: 0..3, tests/test_gpu_pipeline.py)
   if (const char* og = getenv("RAFTSTEP_OVERLAP_GENERAL")) e->overlap_general = std::min(3, std::max(0, atoi(og)));
@@ -873,6 +888,8 @@ int raft_init_steady(raft_engine* e, int32_t leader, int64_t tick0) {
   HIPCHK(hipStreamSynchronize(e->stream));
   state_replaced(e);
   e->steady_origin = true;   // empty logs; the list skip still needs a call that proves the list empty
+  e->phase_ok = e->phase_done = true;   // entry 1 in the global phase of a call at tick0 + 1 (k_init.hip)
+  e->phase_next = tick0 + 1;
   return RAFT_OK;
 }
 
@@ -1296,6 +1313,11 @@ static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool s
   }
   e->run_next = first_tick + int64_t(nticks);
   e->run_done = false;
+  // the ring phase proof (raft_engine::phase_ok) survives only a call that
+  // starts where the last one ended, after a call that issued everything
+  if (first_tick != e->phase_next || !e->phase_done) e->phase_ok = false;
+  e->phase_next = first_tick + int64_t(nticks);
+  e->phase_done = false;
   const Trace T0 = make_trace(e, first_tick);
   int64_t win_first = first_tick;   // first tick of the current general-kernel window
   // steady-state list skip (see raft_engine): entries per tick at most E, so
@@ -1321,6 +1343,12 @@ static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool s
   // was 2% / 9% slower than equal halves)
   const uint64_t Gs = e->cfg.groups;
   const uint64_t half = (Gs / 2) & ~uint64_t(255);
+  // the lean kernel's steady form (see raft_engine::steady_form): device
+  // counters and timing diagnostics keep the general body, and so does the
+  // shared ring in slot chunks (it needs corruption configured: no list skip)
+  const bool steady = two && skip_list && fuse == 1 && e->steady_form && e->phase_ok && !e->P.dbg && !e->P.diag &&
+                      e->P.sh_cs == 0;
+  if (steady) e->n_steady_ticks += nticks;
   const bool split = two && skip_list && fuse == 1 && e->split_steady && half >= 65536 && Gs - half >= 65536;
 
   bool half_busy = false;   // the half stream has work the engine stream has not joined
@@ -1444,10 +1472,13 @@ static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool s
       const int sem = int(e->cfg.semantics);
       if (split) {   // the two halves on two streams (the span's stop event is recorded after the join)
         HIPCHK(launch_tick_lean(e->R, sem, e->P, T, st, e->blist[L], lcount(e, L), 0, e->stream, a,
-                                nullptr, 0, half));
+                                nullptr, 0, half, nullptr, steady));
         HIPCHK(launch_tick_lean(e->R, sem, e->P, T, st, e->blist[L], lcount(e, L), 0, e->half_stream,
-                                nullptr, nullptr, half, Gs - half));
+                                nullptr, nullptr, half, Gs - half, nullptr, steady));
         half_busy = true;
+      } else if (steady) {   // (the list is skipped: the lean kernel alone, as launch_tick_two_pass would)
+        HIPCHK(launch_tick_lean(e->R, sem, e->P, T, st, e->blist[L], lcount(e, L), 0, e->stream, a, b, 0, ~0ull,
+                                nullptr, true));
       } else {
         HIPCHK(launch_tick_two_pass(e->R, int(e->cfg.semantics), e->P, T, st, e->work[e->wpar % NWORK],
                                     e->work_tick[e->wpar % NWORK], cnt, e->blist[L], lcount(e, L),
@@ -1568,6 +1599,7 @@ static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool s
   if (e->P.vx) e->vx_tick = first_tick + int64_t(nticks);
   e->sh_done = true;
   e->run_done = true;
+  e->phase_done = true;
   if (e->comm && e->comm_side) {   // the engine stream (readback, next call) waits for the side-stream sums
     HIPCHK(hipEventRecord(e->comm_ev[1], e->comm_stream));
     HIPCHK(hipStreamWaitEvent(e->stream, e->comm_ev[1], 0));
@@ -1712,12 +1744,12 @@ int raft_tick(raft_engine* e, int64_t first_tick, uint32_t nticks, raft_tick_sta
     if (two) {
       const unsigned long long* c = e->hrb + size_t(nticks) * NSTAT;
       if (c[CHK_MAGIC] != 0x5241465443484Bull) {
-        e->steady_ok = false;
+        e->steady_ok = e->phase_ok = false;
         return fail(RAFT_EINTERNAL, "end-of-call check record missing");
       }
       if (e->skipped_list && c[CHK_LISTED]) {   // (the check block zeroed the list counters)
         e->poisoned = true;
-        e->steady_ok = false;
+        e->steady_ok = e->phase_ok = false;
         e->poison_msg = "steady-state list skip: " + std::to_string(c[CHK_LISTED]) +
                         " groups were passed to a list kernel that did not run (ticks lost)";
         return fail(RAFT_EINTERNAL, "%s", e->poison_msg.c_str());
@@ -1787,7 +1819,7 @@ int raft_append_entries_batch(raft_engine* e, int64_t now_tick, const raft_ae_re
   if (int rc = settle_check(e)) return rc;
   if (int rc = ring_flush(e)) return rc;
   e->run_valid = false;   // host mutation: entries from here on are not the trace's
-  e->steady_origin = e->steady_ok = false;   // host mutation (the list skip needs a fresh proof)
+  e->steady_origin = e->steady_ok = e->phase_ok = false;   // host mutation (the list skip needs a fresh proof)
   if (n == 0) return RAFT_OK;
   if (int rc = check_distinct(e, &reqs[0].group, sizeof(raft_ae_req), n)) return rc;
   std::vector<DevOp> ops(n);
@@ -1842,7 +1874,7 @@ int raft_request_vote_batch(raft_engine* e, int64_t now_tick, const raft_vote_re
   if (int rc = settle_check(e)) return rc;
   if (int rc = ring_flush(e)) return rc;
   e->run_valid = false;   // host mutation: entries from here on are not the trace's
-  e->steady_origin = e->steady_ok = false;   // host mutation (the list skip needs a fresh proof)
+  e->steady_origin = e->steady_ok = e->phase_ok = false;   // host mutation (the list skip needs a fresh proof)
   if (n == 0) return RAFT_OK;
   if (int rc = check_distinct(e, &reqs[0].group, sizeof(raft_vote_req), n)) return rc;
   std::vector<DevOp> ops(n);
@@ -1875,7 +1907,7 @@ int raft_group_ops_batch(raft_engine* e, int64_t now_tick, const raft_group_op* 
   if (int rc = settle_check(e)) return rc;
   if (int rc = ring_flush(e)) return rc;
   e->run_valid = false;   // host mutation: entries from here on are not the trace's
-  e->steady_origin = e->steady_ok = false;   // host mutation (the list skip needs a fresh proof)
+  e->steady_origin = e->steady_ok = e->phase_ok = false;   // host mutation (the list skip needs a fresh proof)
   if (n == 0) return RAFT_OK;
   if (int rc = check_distinct(e, &ops_in[0].group, sizeof(raft_group_op), n)) return rc;
   std::vector<DevOp> ops(n);
@@ -2045,7 +2077,7 @@ int raft_diag_enable(raft_engine* e, int on) {
   }
   if (e->dbg_buf) HIPCHK(hipMemsetAsync(e->dbg_buf, 0, RAFT_DIAG_DEVICE_COUNTERS * 8, e->stream));
   e->P.dbg = on ? e->dbg_buf : nullptr;   // (the buffer stays allocated; counting stops)
-  e->n_ticks = e->n_skip_ticks = e->n_general = 0;
+  e->n_ticks = e->n_skip_ticks = e->n_general = e->n_steady_ticks = 0;
   HIPCHK(hipStreamSynchronize(e->stream));
   return RAFT_OK;
 }
@@ -2063,7 +2095,8 @@ int raft_diag_read(raft_engine* e, uint64_t* counters, uint32_t n) {
   all[RAFT_DIAG_TICKS] = e->n_ticks;
   all[RAFT_DIAG_TICKS_LIST_SKIPPED] = e->n_skip_ticks;
   all[RAFT_DIAG_GENERAL_LAUNCHES] = e->n_general;
-  e->n_ticks = e->n_skip_ticks = e->n_general = 0;
+  all[RAFT_DIAG_TICKS_STEADY_FORM] = e->n_steady_ticks;
+  e->n_ticks = e->n_skip_ticks = e->n_general = e->n_steady_ticks = 0;
   for (uint32_t i = 0; i < n; ++i) counters[i] = all[i];
   return RAFT_OK;
 }

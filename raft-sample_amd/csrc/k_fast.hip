@@ -1,6 +1,7 @@
 // k_fast.hip — the steady-state tick kernel (the metric path).
 #include <cstdlib>
 #include "tick_common.hpp"
+#include "tick_steady.hpp"
 
 namespace raftstep {
 
@@ -1833,8 +1834,8 @@ __global__ __launch_bounds__(LB) void tick_list_kernel(DevPlanes P, Trace T, uns
 #define RAFTSTEP_LEAN_HOIST_LX 1
 #endif
 template <int R, bool CRC, int SEM>
-__global__ __launch_bounds__(256) void tick_lean_kernel(DevPlanes P, Trace T, unsigned long long* stats, uint32_t* list,
-                                                        uint32_t* count, int lflags, uint32_t gofs, uint32_t* zc) {
+__device__ __forceinline__ void lean_tick(const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* list,
+                                          uint32_t* count, int lflags, uint32_t gofs, uint32_t* zc) {
   constexpr bool RAFT = SEM == SEM_RAFT;
   shard_zero(zc);   // (ping-pong pipelined tick: the counter of the next tick's list, read by no running kernel)
   // (gofs: the first group of this launch, a multiple of 256 — the steady
@@ -2296,6 +2297,21 @@ __global__ __launch_bounds__(256) void tick_lean_kernel(DevPlanes P, Trace T, un
   }
 }
 
+// The one-tick lean kernel: the general body above, or (STEADY) the steady
+// form of tick_steady.hpp, which a list-skipping call runs while the engine
+// can prove every live group in the global ring phase (engine.cpp,
+// raft_engine::phase_ok; SH: the entries go to the shared ring). One kernel
+// name for both, so that profiles and the bench's kernel filters see the
+// headline's kernel whichever body it runs.
+template <int R, bool CRC, int SEM, bool STEADY = false, bool SH = false>
+__global__ __launch_bounds__(256) void tick_lean_kernel(std::conditional_t<STEADY, SteadyPlanes, DevPlanes> P,
+                                                        std::conditional_t<STEADY, SteadyTick, Trace> T,
+                                                        unsigned long long* stats, uint32_t* list, uint32_t* count,
+                                                        int lflags, uint32_t gofs, uint32_t* zc) {
+  if constexpr (STEADY) steady_tick<R, CRC, SEM == SEM_RAFT, SH>(P, T, stats, list, count, gofs);
+  else lean_tick<R, CRC, SEM>(P, T, stats, list, count, lflags, gofs, zc);
+}
+
 // Fused steady ticks (the steady-state list skip, engine.cpp): every live
 // group is proven compressed and takeable and no isolation or corruption is
 // configured, so the lean kernel's normal class is the whole tick of every
@@ -2480,8 +2496,19 @@ hipError_t launch_tick_fast(int R, int sem, const DevPlanes& P, const Trace& T, 
 template <int R, bool CRC, int SEM>
 static void launch_lean_t(const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* list,
                           uint32_t* count, int lflags, hipStream_t s, hipEvent_t a, hipEvent_t b, uint64_t g0 = 0,
-                          uint64_t ng = ~0ull, uint32_t* zc = nullptr) {
+                          uint64_t ng = ~0ull, uint32_t* zc = nullptr, bool steady = false) {
   const uint64_t n = std::min<uint64_t>(ng, P.G - g0);
+  if (steady) {   // (the engine's gate: list skipped, no device counters, every live group in phase)
+    const SteadyPlanes SP = steady_planes(P);
+    const SteadyTick ST = steady_tick_args(P, T);
+    if (P.sh)
+      hipExtLaunchKernelGGL((tick_lean_kernel<R, CRC, SEM, true, true>), grid_for(n), dim3(256), 0, s, a, b, 0, SP, ST,
+                            stats, list, count, 0, uint32_t(g0), static_cast<uint32_t*>(nullptr));
+    else
+      hipExtLaunchKernelGGL((tick_lean_kernel<R, CRC, SEM, true, false>), grid_for(n), dim3(256), 0, s, a, b, 0, SP, ST,
+                            stats, list, count, 0, uint32_t(g0), static_cast<uint32_t*>(nullptr));
+    return;
+  }
   hipExtLaunchKernelGGL(tick_lean_kernel<R, CRC, SEM>, grid_for(n), dim3(256), 0, s, a, b, 0, P, T, stats, list,
                         count, lflags, uint32_t(g0), zc);
 }
@@ -2537,15 +2564,15 @@ hipError_t launch_tick_two_pass(int R, int sem, const DevPlanes& P, const Trace&
 }
 hipError_t launch_tick_lean(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* list,
                             uint32_t* count, int lflags, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
-                            uint64_t g0, uint64_t ng, uint32_t* zero_count) {
+                            uint64_t g0, uint64_t ng, uint32_t* zero_count, bool steady) {
   const bool crc = P.crc_on != 0;
 #define RAFT_LEAN(CRC_)                                                                                          \
   if (sem == SEM_RAFT) {                                                                                          \
     RAFT_DISPATCH_R(R, (launch_lean_t<RR, CRC_, SEM_RAFT>(P, T, stats, list, count, lflags, s, ev_start, ev_stop,   \
-                                                          g0, ng, zero_count)))                                   \
+                                                          g0, ng, zero_count, steady)))                           \
   } else {                                                                                                        \
     RAFT_DISPATCH_R(R, (launch_lean_t<RR, CRC_, SEM_REF>(P, T, stats, list, count, lflags, s, ev_start, ev_stop,    \
-                                                         g0, ng, zero_count)))                                    \
+                                                         g0, ng, zero_count, steady)))                            \
   }
   if (crc) { RAFT_LEAN(true); } else { RAFT_LEAN(false); }
 #undef RAFT_LEAN

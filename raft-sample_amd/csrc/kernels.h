@@ -68,10 +68,13 @@ struct ListNext {
 hipError_t launch_tick_fused(int R, int sem, const DevPlanes& P, const Trace& T, int nticks, unsigned long long* stats,
                              uint32_t* list, uint32_t* count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
 // (g0, ng: the launch covers groups [g0, g0 + ng) only; g0 a multiple of 256;
-// zero_count: list counters the launch zeroes, block 0, before anything else)
+// zero_count: list counters the launch zeroes, block 0, before anything else;
+// steady: the kernel's steady form (tick_steady.hpp) — only for a tick of a
+// list-skipping call with every live group in the global ring phase, no
+// device counters and no timing diagnostics; lflags and zero_count unused)
 hipError_t launch_tick_lean(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* list,
                             uint32_t* count, int lflags, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
-                            uint64_t g0 = 0, uint64_t ng = ~0ull, uint32_t* zero_count = nullptr);
+                            uint64_t g0 = 0, uint64_t ng = ~0ull, uint32_t* zero_count = nullptr, bool steady = false);
 
 hipError_t launch_tick_list(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
                             int32_t* work_tick, uint32_t* work_count, uint32_t* list, uint32_t* count,

@@ -148,8 +148,6 @@ struct raft_engine {
   int gen_parity = 0;           // its worklist parity
   uint32_t gen_w0 = 0, gen_w1 = 0;   // its window's stats range (indices into the call's ticks)
   uint32_t gen_join = 0;        // the call's tick index after whose launches the engine stream joins it
-  uint32_t gen_top = 0;         // the last tick index it counts stats into
-  bool gen_stats = false;       // it counts into those per-tick slots of hist
   // per-tick atomic slots of hist a call may have counted into and not
   // reduced (the reduce re-zeroes what it reads): set when a call with
   // statistics starts launching, cleared when it has issued every reduce; a
@@ -399,13 +397,17 @@ int settle_check(raft_engine* e) {
   return RAFT_OK;
 }
 
+// A handler batch changes the state from the host.
+void host_mutation(raft_engine* e) {
+  e->run_valid = false;   // entries from here on are not the trace's
+  e->steady_origin = e->steady_ok = e->phase_ok = false;   // (the list skip needs a fresh proof)
+}
 // A call that replaces the state starts by dropping the list-skip proof (the
 // conservative direction, whatever happens next) ...
 void state_replacing(raft_engine* e) {
-  e->steady_origin = e->steady_ok = e->phase_ok = false;
+  host_mutation(e);
   e->vx_live = false;   // (the state is being replaced: no suffix survives)
   e->sh_live = false;   // (nor a shared entry: every rotation is rewritten)
-  e->run_valid = false;
 }
 // ... and only once the new state's launches / copies have gone through
 // successfully drops any poison and a still-pending end-of-call check (both
@@ -1254,7 +1256,92 @@ static int join_general(raft_engine* e, bool stats, hipStream_t s = nullptr) {
 // Stream of tick i of a ping-pong call (raft_engine::pingpong).
 static hipStream_t pp_stream(const raft_engine* e, uint32_t i) { return (i & 1u) ? e->list_stream : e->stream; }
 
-static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool stats) {
+// What a raft_tick call decides before its first launch (plan_call, which
+// changes nothing on the engine): the form its ticks take and on which streams.
+enum class TickMode { Fused, Pipelined, Inline, Skip, Fast };
+struct CallPlan {
+  int64_t first_tick;
+  uint32_t nticks;   // (> 0)
+  bool stats;
+  Trace T0;          // the trace of the call's first tick
+  bool skip_list;    // steady-state list skip (see raft_engine)
+  bool two;          // two-pass tick (lean + list kernels), else the single fast kernel
+  bool call_lean;    // the lean (or fused) kernel runs over every group: the base of the call's statistics
+  bool pipe, pp;     // pipelined tick (raft_engine::pipeline), on ping-pong streams (raft_engine::pingpong)
+  uint32_t fuse;     // ticks per launch (1: no fused launches)
+  uint64_t Gs, half; // split steady tick: the groups, and those of the engine stream's half
+  bool steady, split;   // the lean kernel's steady form (raft_engine::steady_form); split steady tick (split_steady)
+  TickMode mode;
+};
+
+static CallPlan plan_call(const raft_engine* e, int64_t first_tick, uint32_t nticks, bool stats) {
+  CallPlan p{first_tick, nticks, stats, make_trace(e, first_tick)};
+  // steady-state list skip (see raft_engine): entries per tick at most E, so
+  // LastApplied + E stays below 2^31 while E * (last tick + 2) does
+  p.skip_list = e->steady_ok && e->steady_origin && p.T0.iso_p == 0 && e->P.corrupt_p == 0 && !e->force_general &&
+                uint64_t(e->cfg.entries_per_tick) < e->cfg.ring_depth &&
+                double(e->cfg.entries_per_tick) * double(first_tick + int64_t(nticks) + 2) < 2.0e9;
+  p.two = e->two_pass && !e->force_general;
+  p.call_lean = p.two && p.T0.iso_p == 0;   // (under isolation churn the lean kernel counts absolutely)
+  p.pipe = p.two && !p.skip_list && !e->debug_work && e->pipeline;
+  p.pp = p.pipe && e->pingpong;
+  p.fuse = (p.two && p.skip_list && !e->cfg.payload_crc && e->prof != 3) ? e->fuse : 1u;
+  // split steady tick (see raft_engine::split_steady): halves of whole
+  // 256-group blocks (A/B, round 4: giving the half stream 45% or 40% of the
+  // groups, so that it would run ahead and the call-end join find it done,
+  // was 2% / 9% slower than equal halves)
+  p.Gs = e->cfg.groups;
+  p.half = (p.Gs / 2) & ~uint64_t(255);
+  const bool lean_alone = p.two && p.skip_list && p.fuse == 1;   // one lean launch (or its two halves) per tick
+  // the lean kernel's steady form (see raft_engine::steady_form): device
+  // counters and timing diagnostics keep the general body, and so does the
+  // shared ring in slot chunks (it needs corruption configured: no list skip)
+  p.steady = lean_alone && e->steady_form && e->phase_ok && !e->P.dbg && !e->P.diag && e->P.sh_cs == 0;
+  p.split = lean_alone && e->split_steady && p.half >= 65536 && p.Gs - p.half >= 65536;
+  p.mode = p.fuse > 1 ? TickMode::Fused : p.pipe ? TickMode::Pipelined : !p.two ? TickMode::Fast
+           : p.skip_list ? TickMode::Skip : TickMode::Inline;
+  return p;
+}
+
+// The loop state of one call.
+struct CallState {
+  int64_t win_first;          // first tick of the current general-kernel window
+  uint32_t stats_first = 0;   // first tick (index in this call) whose records are not reduced yet
+  bool half_busy = false;     // the half stream has work the engine stream has not joined
+  hipEvent_t prof_a = nullptr, prof_b = nullptr;   // profile mode 1, steady calls: the span of the call's launches
+  hipEvent_t ra = nullptr, rb = nullptr;           // profile mode 2: around the call's launches
+};
+// One tick of it: index in the call, trace, stats record, the worklist counter
+// of its window (zeroed by the previous general kernel, or at engine creation,
+// so no per-call memset), and the profile events of its dispatches (may be
+// null): a / b the lean, fused or fast kernel's, c / d the list kernel's.
+struct Tick {
+  uint32_t i;
+  Trace T;
+  unsigned long long* st;
+  uint32_t* cnt;
+  hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr;
+};
+
+// The engine stream joins the half stream, before a reduce and at the end of
+// the call. Profile mode 1: the span of a split call's launches ends with both
+// halves, before the reduce (raftstep.h; a split call reduces once, at its end).
+static int join_half(raft_engine* e, const CallPlan& p, CallState& cs) {
+  if (cs.half_busy) {
+    HIPCHK(hipEventRecord(e->ev_half[1], e->half_stream));
+    HIPCHK(hipStreamWaitEvent(e->stream, e->ev_half[1], 0));
+    cs.half_busy = false;
+  }
+  if (p.split && cs.prof_b) {
+    HIPCHK(hipEventRecord(cs.prof_b, e->stream));
+    cs.prof_b = nullptr;
+  }
+  return RAFT_OK;
+}
+
+// Before a call's plan: the last call's checks and leftovers, this call's range
+// checks (a call of no ticks ends there), the VX / SH / run / ring phase records.
+static int tick_begin(raft_engine* e, int64_t first_tick, uint32_t nticks, bool stats) {
   if (int rc = settle_check(e)) return rc;
   if (int rc = check_ticks(e, first_tick, nticks)) return rc;
   HIPCHK(hipSetDevice(e->cfg.device));
@@ -1318,285 +1405,279 @@ static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool s
   if (first_tick != e->phase_next || !e->phase_done) e->phase_ok = false;
   e->phase_next = first_tick + int64_t(nticks);
   e->phase_done = false;
-  const Trace T0 = make_trace(e, first_tick);
-  int64_t win_first = first_tick;   // first tick of the current general-kernel window
-  // steady-state list skip (see raft_engine): entries per tick at most E, so
-  // LastApplied + E stays below 2^31 while E * (last tick + 2) does
-  const bool skip_list = e->steady_ok && e->steady_origin && T0.iso_p == 0 && e->P.corrupt_p == 0 &&
-                         !e->force_general && uint64_t(e->cfg.entries_per_tick) < e->cfg.ring_depth &&
-                         double(e->cfg.entries_per_tick) * double(first_tick + int64_t(nticks) + 2) < 2.0e9;
-  e->skipped_list = skip_list;
-  e->n_ticks += nticks;
-  if (skip_list) e->n_skip_ticks += nticks;
-  const bool two = e->two_pass && !e->force_general;
-  e->call_t0 = first_tick;
-  e->call_lean = two && T0.iso_p == 0;   // (under isolation churn the lean kernel counts absolutely)
-  const bool pipe = two && !skip_list && !e->debug_work && e->pipeline;
-  const bool pp = pipe && e->pingpong;
-  if (e->debug_pipe)
-    fprintf(stderr, "raftstep: ticks %lld..%lld pipeline %d\n", (long long)first_tick,
-            (long long)(first_tick + nticks - 1), int(pipe));
-  const uint32_t fuse = (two && skip_list && !e->cfg.payload_crc && e->prof != 3) ? e->fuse : 1u;
-  // split steady tick (see raft_engine::split_steady): halves of whole
-  // 256-group blocks (A/B, round 4: giving the half stream 45% or 40% of the
-  // groups, so that it would run ahead and the call-end join find it done,
-  // was 2% / 9% slower than equal halves)
-  const uint64_t Gs = e->cfg.groups;
-  const uint64_t half = (Gs / 2) & ~uint64_t(255);
-  // the lean kernel's steady form (see raft_engine::steady_form): device
-  // counters and timing diagnostics keep the general body, and so does the
-  // shared ring in slot chunks (it needs corruption configured: no list skip)
-  const bool steady = two && skip_list && fuse == 1 && e->steady_form && e->phase_ok && !e->P.dbg && !e->P.diag &&
-                      e->P.sh_cs == 0;
-  if (steady) e->n_steady_ticks += nticks;
-  const bool split = two && skip_list && fuse == 1 && e->split_steady && half >= 65536 && Gs - half >= 65536;
+  return RAFT_OK;
+}
 
-  bool half_busy = false;   // the half stream has work the engine stream has not joined
-  auto join_half = [&]() -> int {
-    if (!half_busy) return RAFT_OK;
-    HIPCHK(hipEventRecord(e->ev_half[1], e->half_stream));
-    HIPCHK(hipStreamWaitEvent(e->stream, e->ev_half[1], 0));
-    half_busy = false;
-    return RAFT_OK;
-  };
+// The profile events of tick k: mode 1 times the lean / fused / fast dispatch
+// (a, b), mode 3 the list kernel's (c, d).
+static int tick_events(raft_engine* e, const CallPlan& p, CallState& cs, Tick& k) {
+  const bool fused = p.fuse > 1;
+  if (e->prof == 1 && p.skip_list) {
+    // steady calls (the lean or fused kernel alone, back to back): one
+    // event pair spanning the call's launches — the start event on the
+    // first dispatch, the stop event on the last — so that the kernels
+    // run exactly as in the timed region (an event pair on every dispatch
+    // puts ~9 us between them, and a kernel that starts on a drained
+    // device runs ~1 us shorter than back to back)
+    const uint32_t last_launch = fused ? (p.nticks - 1) / p.fuse * p.fuse : p.nticks - 1;
+    if (k.i == 0) {
+      cs.prof_a = next_event(e);
+      cs.prof_b = next_event(e);
+      if (!cs.prof_a || !cs.prof_b) return fail(RAFT_EHIP, "hipEventCreate failed");
+      e->ev_ticks.push_back(p.nticks);
+      k.a = cs.prof_a;
+    }
+    if (k.i == last_launch && !p.split) k.b = cs.prof_b;   // (split: recorded after the halves' join)
+  } else if (e->prof == 1 && (!fused || k.i % p.fuse == 0)) {
+    k.a = next_event(e);
+    k.b = next_event(e);
+    if (!k.a || !k.b) return fail(RAFT_EHIP, "hipEventCreate failed");
+    e->ev_ticks.push_back(fused ? std::min<uint32_t>(p.fuse, p.nticks - k.i) : 1u);
+  }
+  if (e->prof == 3 && (p.mode == TickMode::Pipelined || p.mode == TickMode::Inline)) {
+    k.c = next_event(e);
+    k.d = next_event(e);
+    if (!k.c || !k.d) return fail(RAFT_EHIP, "hipEventCreate failed");
+  }
+  return RAFT_OK;
+}
+
+// Fused steady ticks: one launch per `fuse` ticks (its first), stats of each
+// tick in its own record; the list counters rotate per tick as usual.
+static int tick_fused(raft_engine* e, const CallPlan& p, const Tick& k) {
+  if (k.i % p.fuse == 0)
+    HIPCHK(launch_tick_fused(e->R, int(e->cfg.semantics), e->P, k.T, int(std::min<uint32_t>(p.fuse, p.nticks - k.i)),
+                             k.st, e->blist[e->lpar % 3], lcount(e, e->lpar % 3), e->stream, k.a, k.b));
+  ++e->lpar;
+  return RAFT_OK;
+}
+// Pipelined tick: lean(t) appends to list L; list(t) reads it, zeroes list L+2
+// (last read by list(t-1), next filled by lean(t+2), which waits for list(t)).
+static int tick_pipelined(raft_engine* e, const CallPlan& p, const Tick& k) {
+  const uint32_t i = k.i, L = e->lpar % 3, w = e->wpar % NWORK;
+  const int sem = int(e->cfg.semantics);
+  const bool carry = i + 1 < p.nticks;   // list(t) runs its groups through t+1 too
+  const int lflags = (i > 0 ? 1 : 0) | (carry ? 2 : 0);
+  // (ping-pong: lean(t) after lean(t-1) on the other stream; list(t-2),
+  // which carried its groups through t-1, is before it on its own)
+  hipStream_t ls = p.pp ? pp_stream(e, i) : e->stream;        // lean(t)'s stream
+  hipStream_t qs = p.pp ? ls : e->list_stream;                // list(t)'s
+  if (p.pp) {
+    if (i >= 1) HIPCHK(hipStreamWaitEvent(ls, e->ev_lean[(i - 1) & 1], 0));
+  } else if (i >= 2) {
+    HIPCHK(hipStreamWaitEvent(e->stream, e->ev_list[(i - 2) & 3], 0));   // carried its groups through t-1
+  }
+  // (ping-pong: the events are the kernels' own stop events — no marker
+  // packet between lean(t) and list(t): C4 +2.5% in an A/B, round 4 — unless
+  // a profile event takes the kernel's stop slot)
+  const bool lean_own = p.pp && !k.b, list_own = p.pp && !k.d;
+  HIPCHK(launch_tick_lean(e->R, sem, e->P, k.T, k.st, e->blist[L], lcount(e, L), lflags, ls, k.a,
+                          lean_own ? e->ev_lean[i & 1] : k.b, 0, ~0ull, p.pp ? lcount(e, (L + 1) % 3) : nullptr));
+  if (!lean_own) HIPCHK(hipEventRecord(e->ev_lean[i & 1], ls));
+  if (!p.pp) HIPCHK(hipStreamWaitEvent(e->list_stream, e->ev_lean[i & 1], 0));
+  ListNext nx{};
+  if (carry) {   // tick t+1: its stats record, the worklist of its window
+    const int np = int((e->wpar + ((i + 1) % e->slow_every == 0 ? 1u : 0u)) % NWORK);
+    nx = ListNext{p.stats ? k.st + size_t(STAT_TICK) : nullptr, e->work[np], e->work_tick[np],
+                  e->wcount + np * SHARD_WORDS};
+  }
+  // (the call's last list kernel zeroes nothing: list L+2 then still
+  // counts the groups list(t-1) carried into this tick, which the
+  // end-of-call check counts as listed at the last tick; every pipelined
+  // call starts with the three lists' counters zeroed)
+  HIPCHK(launch_tick_list(e->R, sem, e->P, k.T, k.st, e->work[w], e->work_tick[w], k.cnt, e->blist[L], lcount(e, L),
+                          (carry && !p.pp) ? lcount(e, (L + 2) % 3) : nullptr, carry ? &nx : nullptr, qs, k.c,
+                          list_own ? e->ev_list[i & 3] : k.d));
+  if (!list_own) HIPCHK(hipEventRecord(e->ev_list[i & 3], qs));
+  ++e->lpar;
+  return RAFT_OK;
+}
+// In-line two-pass tick (RAFTSTEP_PIPELINE=0): the lean pass appends to list
+// counter lpar, the list pass after it on the engine stream zeroes list L+2.
+static int tick_inline(raft_engine* e, const Tick& k) {
+  const uint32_t L = e->lpar % 3, w = e->wpar % NWORK;
+  const int sem = int(e->cfg.semantics);
+  HIPCHK(launch_tick_lean(e->R, sem, e->P, k.T, k.st, e->blist[L], lcount(e, L), 0, e->stream, k.a, k.b));
+  HIPCHK(launch_tick_list(e->R, sem, e->P, k.T, k.st, e->work[w], e->work_tick[w], k.cnt, e->blist[L], lcount(e, L),
+                          lcount(e, (L + 2) % 3), nullptr, e->stream, k.c, k.d));
+  ++e->lpar;
+  return RAFT_OK;
+}
+// List-skipping tick: the lean kernel alone, steady form or not, over every group or
+// over the two halves on two streams (the span's stop event is recorded after the join).
+static int tick_skip(raft_engine* e, const CallPlan& p, CallState& cs, const Tick& k) {
+  const uint32_t L = e->lpar % 3;
+  const int sem = int(e->cfg.semantics);
+  HIPCHK(launch_tick_lean(e->R, sem, e->P, k.T, k.st, e->blist[L], lcount(e, L), 0, e->stream, k.a,
+                          p.split ? nullptr : k.b, 0, p.split ? p.half : ~0ull, nullptr, p.steady));
+  if (p.split) {
+    HIPCHK(launch_tick_lean(e->R, sem, e->P, k.T, k.st, e->blist[L], lcount(e, L), 0, e->half_stream, nullptr,
+                            nullptr, p.half, p.Gs - p.half, nullptr, p.steady));
+    cs.half_busy = true;
+  }
+  ++e->lpar;
+  return RAFT_OK;
+}
+static int tick_fast(raft_engine* e, const Tick& k) {
+  const uint32_t w = e->wpar % NWORK;
+  HIPCHK(launch_tick_fast(e->R, int(e->cfg.semantics), e->P, k.T, k.st, e->work[w], e->work_tick[w], k.cnt,
+                          e->force_general, e->stream, k.a, k.b));
+  return RAFT_OK;
+}
+
+// The previous window's general kernel, overlapped with tick i's fast
+// kernels: the engine stream waits for it, then its window tail clears
+// its groups' DEFER (before the next tick's lean kernel) and its ticks'
+// records are final.
+static int join_due_general(raft_engine* e, const CallPlan& p, uint32_t i) {
+  if (!e->gen_pending || i < e->gen_join) return RAFT_OK;
+  // (ping-pong: on the stream of lean(t+1), after lean(t))
+  hipStream_t js = p.pp ? pp_stream(e, i + 1) : e->stream;
+  if (p.pp) HIPCHK(hipStreamWaitEvent(js, e->ev_lean[i & 1], 0));
+  return join_general(e, p.stats, js);
+}
+
+// End of a window, the general kernel: deferred groups catch up on worklist
+// `par`, beside the following ticks (*overlap) or in line.
+static int window_general(raft_engine* e, const CallPlan& p, const CallState& cs, const Tick& k, int par,
+                          bool* overlap) {
+  const uint32_t i = k.i;
+  const int64_t t = p.first_tick + int64_t(i);
+  if (e->debug_work) {   // diagnostics: worklist size of each general-kernel launch (synchronising)
+    uint32_t sh[SHARD_WORDS], nw = 0;
+    HIPCHK(hipMemcpyAsync(sh, k.cnt, sizeof sh, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int j = 0; j < NSHARD; ++j) nw += sh[j * SHARD_STRIDE];
+    fprintf(stderr, "raftstep: general kernel ticks %lld..%lld worklist %u\n", (long long)cs.win_first, (long long)t, nw);
+  }
+  // pipelined: the window's deferrals are complete once list(t) is done
+  // (its second step, tick t+1, defers to the next window's worklist)
+  hipStream_t after = p.pipe ? e->list_stream : e->stream;
+  // (with the list skipped nothing can be deferred — only the list kernel
+  // defers — so both worklists stay empty and there is nothing to catch up)
+  // (pipelined, a window's general kernel must run through tick t+1 and
+  // its tail come after the lean kernel of t+1, which leaves the groups
+  // list(t) passed on alone even when list(t) deferred them at tick t:
+  // so the pipeline always takes this form)
+  *overlap = !p.skip_list && p.two && (e->overlap_general || p.pipe) && i + 1 != p.nticks && !e->debug_work;
+  unsigned long long* hist = p.stats ? e->hist : nullptr;
+  if (*overlap) {
+    // beside the lean and list kernels of ticks t+1 .. t+d, through tick
+    // t+d (its groups keep DEFER, so those kernels leave them alone; their
+    // deferrals go to the other worklist): d = the overlap depth, within
+    // the call and at most one window (the next window's general kernel
+    // starts after this one has joined)
+    const uint32_t d = std::min<uint32_t>({uint32_t(std::max(e->overlap_general, 1)), e->slow_every, p.nticks - 1 - i});
+    if (p.pp) {   // ping-pong: list(t) and list(t-1) (tick t's deferrals) are on the two streams
+      HIPCHK(hipStreamWaitEvent(e->gen_stream, e->ev_list[i & 3], 0));
+      if (i >= 1) HIPCHK(hipStreamWaitEvent(e->gen_stream, e->ev_list[(i - 1) & 3], 0));
+    } else {
+      HIPCHK(hipEventRecord(e->gen_ev[0], after));
+      HIPCHK(hipStreamWaitEvent(e->gen_stream, e->gen_ev[0], 0));
+    }
+    HIPCHK(launch_tick_slow(e->R, int(e->cfg.semantics), e->P, p.T0, p.first_tick, cs.win_first, t + int64_t(d), hist,
+                            e->work[par], e->work_tick[par], k.cnt, nullptr, e->lane_general, e->gen_stream));
+    HIPCHK(hipEventRecord(e->gen_ev[1], e->gen_stream));
+    e->gen_pending = true;
+    e->gen_parity = par;
+    e->gen_w0 = cs.stats_first;
+    e->gen_w1 = i;
+    e->gen_join = i + d;
+    ++e->n_general;
+  } else if (!p.skip_list) {
+    if (p.pp) {   // everything on list_stream (list(t) or list(t-1), a window join) before the engine stream
+      HIPCHK(hipEventRecord(e->ev_pp, e->list_stream));
+      HIPCHK(hipStreamWaitEvent(e->stream, e->ev_pp, 0));
+    } else if (p.pipe) {
+      HIPCHK(hipStreamWaitEvent(e->stream, e->ev_list[i & 3], 0));
+    }
+    HIPCHK(launch_tick_slow(e->R, int(e->cfg.semantics), e->P, p.T0, p.first_tick, cs.win_first, t, hist,
+                            e->work[par], e->work_tick[par], k.cnt, nullptr, e->lane_general, e->stream));
+    HIPCHK(launch_window_tail(e->P, e->work[par], e->wcount, par, e->stream));
+    ++e->n_general;
+  }
+  return RAFT_OK;
+}
+
+// End of a window: deferred groups catch up every slow_every ticks and at the
+// end of the call (window_general), then the statistics.
+static int end_window(raft_engine* e, const CallPlan& p, CallState& cs, const Tick& k) {
+  const uint32_t i = k.i;
+  const bool last = i + 1 == p.nticks;
+  const int par = int(e->wpar % NWORK);
+  bool overlap = false;
+  if (int rc = window_general(e, p, cs, k, par, &overlap)) return rc;
+  ++e->wpar;
+  // per-tick records: reduced (and all-reduced) per window — an overlapped
+  // window's once its general kernel has joined; with the list skipped
+  // nothing overlaps them, so one reduce (and one all-reduce) at the end of
+  // the call covers every tick (with a communicator too: a per-window
+  // flush costs the split tick a cross-stream join each, 418-424 vs
+  // 366-374 us per 20-tick call, round 4). The last one carries the check
+  // record.
+  CallCheck chk{e->wcount, par, p.skip_list ? 1 : 0, e->tstat + size_t(p.nticks) * NSTAT, int((e->lpar + 2) % 3),
+                nullptr, nullptr, nullptr, 0u};
+  // the call's only reduce (every record in this launch), no communicator:
+  // the records also go straight to the host (CallCheck::hout)
+  e->mirror = p.stats && last && p.two && cs.stats_first == 0 && !e->comm;
+  if (e->mirror) {
+    chk.hout = e->hrb;
+    chk.hdone = e->hdone;
+    chk.ctr = e->dctr;
+    chk.seq = ++e->seq;
+  }
+  const bool wflush = !p.skip_list || last;
+  if (p.stats && !overlap && wflush) {
+    if (int rc = join_half(e, p, cs)) return rc;
+    if (int rc = flush_window_stats(e, cs.stats_first, i, (last && p.two) ? &chk : nullptr, nullptr, last)) return rc;
+  }
+  if (wflush) cs.stats_first = i + 1;
+  cs.win_first = p.first_tick + int64_t(i) + 1;
+  return RAFT_OK;
+}
+
+// The call's launches, tick by tick.
+static int tick_issue(raft_engine* e, const CallPlan& p, CallState& cs) {
   // the half stream starts after everything issued before this call (a
   // cross-stream wait costs ~10 us on the critical path: skipped when the
   // engine stream is idle already, e.g. after a call that read its stats back)
-  if (split && hipStreamQuery(e->stream) != hipSuccess) {
+  if (p.split && hipStreamQuery(e->stream) != hipSuccess) {
     HIPCHK(hipEventRecord(e->ev_half[0], e->stream));
     HIPCHK(hipStreamWaitEvent(e->half_stream, e->ev_half[0], 0));
   }
   // every call that runs list kernels starts with the lists' counters zeroed
   // (a pipelined call's last list kernel leaves the carried list's count)
-  if (two && !skip_list) HIPCHK(hipMemsetAsync(lcount(e, 0), 0, size_t(NLISTS) * SHARD_WORDS * 4, e->stream));
-  uint32_t stats_first = 0;   // first tick (index in this call) whose records are not reduced yet
-  hipEvent_t ra = nullptr, rb = nullptr;
+  if (p.two && !p.skip_list) HIPCHK(hipMemsetAsync(lcount(e, 0), 0, size_t(NLISTS) * SHARD_WORDS * 4, e->stream));
   if (e->prof == 2) {
-    ra = next_event(e);
-    rb = next_event(e);
-    if (!ra || !rb) return fail(RAFT_EHIP, "hipEventCreate failed");
-    HIPCHK(hipEventRecord(ra, e->stream));
+    cs.ra = next_event(e);
+    cs.rb = next_event(e);
+    if (!cs.ra || !cs.rb) return fail(RAFT_EHIP, "hipEventCreate failed");
+    HIPCHK(hipEventRecord(cs.ra, e->stream));
   }
-  hipEvent_t prof_a = nullptr, prof_b = nullptr;   // profile mode 1, steady calls: the span of the call's launches
-  for (uint32_t i = 0; i < nticks; ++i) {
-    const int64_t t = first_tick + int64_t(i);
-    const Trace T = make_trace(e, t);
-    unsigned long long* st = stats ? e->hist + size_t(i) * STAT_TICK : nullptr;
-    // worklist counter of this window; zeroed by the previous general kernel
-    // (or at engine creation), so no per-call memset
-    uint32_t* cnt = e->wcount + (e->wpar % NWORK) * SHARD_WORDS;
-    hipEvent_t a = nullptr, b = nullptr;
-    const bool fused = fuse > 1;
-    if (e->prof == 1 && skip_list) {
-      // steady calls (the lean or fused kernel alone, back to back): one
-      // event pair spanning the call's launches — the start event on the
-      // first dispatch, the stop event on the last — so that the kernels
-      // run exactly as in the timed region (an event pair on every dispatch
-      // puts ~9 us between them, and a kernel that starts on a drained
-      // device runs ~1 us shorter than back to back)
-      const uint32_t last_launch = fused ? (nticks - 1) / fuse * fuse : nticks - 1;
-      if (i == 0) {
-        prof_a = next_event(e);
-        prof_b = next_event(e);
-        if (!prof_a || !prof_b) return fail(RAFT_EHIP, "hipEventCreate failed");
-        e->ev_ticks.push_back(nticks);
-        a = prof_a;
-      }
-      if (i == last_launch && !split) b = prof_b;
-    } else if (e->prof == 1 && (!fused || i % fuse == 0)) {
-      a = next_event(e);
-      b = next_event(e);
-      if (!a || !b) return fail(RAFT_EHIP, "hipEventCreate failed");
-      e->ev_ticks.push_back(fused ? std::min<uint32_t>(fuse, nticks - i) : 1u);
+  for (uint32_t i = 0; i < p.nticks; ++i) {
+    Tick k{i, make_trace(e, p.first_tick + int64_t(i)), p.stats ? e->hist + size_t(i) * STAT_TICK : nullptr,
+           e->wcount + (e->wpar % NWORK) * SHARD_WORDS};
+    int rc = tick_events(e, p, cs, k);
+    if (rc) return rc;
+    switch (p.mode) {
+      case TickMode::Fused: rc = tick_fused(e, p, k); break;
+      case TickMode::Pipelined: rc = tick_pipelined(e, p, k); break;
+      case TickMode::Inline: rc = tick_inline(e, k); break;
+      case TickMode::Skip: rc = tick_skip(e, p, cs, k); break;
+      case TickMode::Fast: rc = tick_fast(e, k); break;
     }
-    const int force = e->force_general;
-    if (fused) {
-      // fused steady ticks: one launch per `fuse` ticks (its first), stats of
-      // each tick in its own record; the list counters rotate per tick as usual
-      if (i % fuse == 0)
-        HIPCHK(launch_tick_fused(e->R, int(e->cfg.semantics), e->P, T, int(std::min<uint32_t>(fuse, nticks - i)), st,
-                                 e->blist[e->lpar % 3], lcount(e, e->lpar % 3), e->stream, a, b));
-      ++e->lpar;
-    } else if (pipe) {
-      // lean(t) appends to list L; list(t) reads it, zeroes list L+2 (last
-      // read by list(t-1), next filled by lean(t+2), which waits for list(t))
-      const uint32_t L = e->lpar % 3;
-      const bool carry = i + 1 < nticks;   // list(t) runs its groups through t+1 too
-      const int lflags = (i > 0 ? 1 : 0) | (carry ? 2 : 0);
-      hipEvent_t c = nullptr, d = nullptr;
-      if (e->prof == 3) {
-        c = next_event(e);
-        d = next_event(e);
-        if (!c || !d) return fail(RAFT_EHIP, "hipEventCreate failed");
-      }
-      // (ping-pong: lean(t) after lean(t-1) on the other stream; list(t-2),
-      // which carried its groups through t-1, is before it on its own)
-      hipStream_t cs = pp ? pp_stream(e, i) : e->stream;
-      if (pp) {
-        if (i >= 1) HIPCHK(hipStreamWaitEvent(cs, e->ev_lean[(i - 1) & 1], 0));
-      } else if (i >= 2) {
-        HIPCHK(hipStreamWaitEvent(e->stream, e->ev_list[(i - 2) & 3], 0));   // carried its groups through t-1
-      }
-      // (ping-pong: the events are the kernels' own stop events — no marker
-      // packet between lean(t) and list(t): C4 +2.5% in an A/B, round 4)
-      const bool evk = pp && !b;
-      HIPCHK(launch_tick_lean(e->R, int(e->cfg.semantics), e->P, T, st, e->blist[L], lcount(e, L), lflags, cs, a,
-                              evk ? e->ev_lean[i & 1] : b, 0, ~0ull, pp ? lcount(e, (L + 1) % 3) : nullptr));
-      if (!evk) HIPCHK(hipEventRecord(e->ev_lean[i & 1], cs));
-      if (!pp) HIPCHK(hipStreamWaitEvent(e->list_stream, e->ev_lean[i & 1], 0));
-      ListNext nx{};
-      if (carry) {   // tick t+1: its stats record, the worklist of its window
-        const int np = int((e->wpar + ((i + 1) % e->slow_every == 0 ? 1u : 0u)) % NWORK);
-        nx = ListNext{stats ? st + size_t(STAT_TICK) : nullptr, e->work[np], e->work_tick[np],
-                      e->wcount + np * SHARD_WORDS};
-      }
-      // (the call's last list kernel zeroes nothing: list L+2 then still
-      // counts the groups list(t-1) carried into this tick, which the
-      // end-of-call check counts as listed at the last tick; every pipelined
-      // call starts with the three lists' counters zeroed)
-      HIPCHK(launch_tick_list(e->R, int(e->cfg.semantics), e->P, T, st, e->work[e->wpar % NWORK], e->work_tick[e->wpar % NWORK],
-                              cnt, e->blist[L], lcount(e, L), (carry && !pp) ? lcount(e, (L + 2) % 3) : nullptr,
-                              carry ? &nx : nullptr, pp ? cs : e->list_stream, c,
-                              (pp && !d) ? e->ev_list[i & 3] : d));
-      if (!(pp && !d)) HIPCHK(hipEventRecord(e->ev_list[i & 3], pp ? cs : e->list_stream));
-      ++e->lpar;
-    } else if (two) {
-      // lean pass appends to list counter lpar, the list pass zeroes the other one
-      hipEvent_t c = nullptr, d = nullptr;
-      if (e->prof == 3 && !skip_list) {
-        c = next_event(e);
-        d = next_event(e);
-        if (!c || !d) return fail(RAFT_EHIP, "hipEventCreate failed");
-      }
-      const uint32_t L = e->lpar % 3;
-      const int sem = int(e->cfg.semantics);
-      if (split) {   // the two halves on two streams (the span's stop event is recorded after the join)
-        HIPCHK(launch_tick_lean(e->R, sem, e->P, T, st, e->blist[L], lcount(e, L), 0, e->stream, a,
-                                nullptr, 0, half, nullptr, steady));
-        HIPCHK(launch_tick_lean(e->R, sem, e->P, T, st, e->blist[L], lcount(e, L), 0, e->half_stream,
-                                nullptr, nullptr, half, Gs - half, nullptr, steady));
-        half_busy = true;
-      } else if (steady) {   // (the list is skipped: the lean kernel alone, as launch_tick_two_pass would)
-        HIPCHK(launch_tick_lean(e->R, sem, e->P, T, st, e->blist[L], lcount(e, L), 0, e->stream, a, b, 0, ~0ull,
-                                nullptr, true));
-      } else {
-        HIPCHK(launch_tick_two_pass(e->R, int(e->cfg.semantics), e->P, T, st, e->work[e->wpar % NWORK],
-                                    e->work_tick[e->wpar % NWORK], cnt, e->blist[L], lcount(e, L),
-                                    lcount(e, (L + 2) % 3), e->stream, a, b, c, d, skip_list));
-      }
-      ++e->lpar;
-    } else {
-      HIPCHK(launch_tick_fast(e->R, int(e->cfg.semantics), e->P, T, st, e->work[e->wpar % NWORK],
-                              e->work_tick[e->wpar % NWORK], cnt, force, e->stream, a, b));
-    }
-    // the previous window's general kernel, overlapped with this tick's fast
-    // kernels: the engine stream waits for it, then its window tail clears
-    // its groups' DEFER (before the next tick's lean kernel) and its ticks'
-    // records are final
-    if (e->gen_pending && i >= e->gen_join) {
-      // (ping-pong: on the stream of lean(t+1), after lean(t))
-      hipStream_t js = pp ? pp_stream(e, i + 1) : e->stream;
-      if (pp) HIPCHK(hipStreamWaitEvent(js, e->ev_lean[i & 1], 0));
-      if (int rc = join_general(e, stats, js)) return rc;
-    }
-    // deferred groups catch up every slow_every ticks and at the end of the call
-    if ((i + 1) % e->slow_every == 0 || i + 1 == nticks) {
-      if (e->debug_work) {   // diagnostics: worklist size of each general-kernel launch (synchronising)
-        uint32_t sh[SHARD_WORDS], nw = 0;
-        HIPCHK(hipMemcpyAsync(sh, cnt, sizeof sh, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        for (int k = 0; k < NSHARD; ++k) nw += sh[k * SHARD_STRIDE];
-        fprintf(stderr, "raftstep: general kernel ticks %lld..%lld worklist %u\n", (long long)win_first, (long long)t, nw);
-      }
-      const bool last = i + 1 == nticks;
-      const int par = int(e->wpar % NWORK);
-      // pipelined: the window's deferrals are complete once list(t) is done
-      // (its second step, tick t+1, defers to the next window's worklist)
-      hipStream_t after = pipe ? e->list_stream : e->stream;
-      // (with the list skipped nothing can be deferred — only the list kernel
-      // defers — so both worklists stay empty and there is nothing to catch up)
-      // (pipelined, a window's general kernel must run through tick t+1 and
-      // its tail come after the lean kernel of t+1, which leaves the groups
-      // list(t) passed on alone even when list(t) deferred them at tick t:
-      // so the pipeline always takes this form)
-      const bool overlap = !skip_list && two && (e->overlap_general || pipe) && !last && !e->debug_work;
-      if (overlap) {
-        // beside the lean and list kernels of ticks t+1 .. t+d, through tick
-        // t+d (its groups keep DEFER, so those kernels leave them alone; their
-        // deferrals go to the other worklist): d = the overlap depth, within
-        // the call and at most one window (the next window's general kernel
-        // starts after this one has joined)
-        const uint32_t d = std::min<uint32_t>({uint32_t(std::max(e->overlap_general, 1)), e->slow_every, nticks - 1 - i});
-        if (pp) {   // ping-pong: list(t) and list(t-1) (tick t's deferrals) are on the two streams
-          HIPCHK(hipStreamWaitEvent(e->gen_stream, e->ev_list[i & 3], 0));
-          if (i >= 1) HIPCHK(hipStreamWaitEvent(e->gen_stream, e->ev_list[(i - 1) & 3], 0));
-        } else {
-          HIPCHK(hipEventRecord(e->gen_ev[0], after));
-          HIPCHK(hipStreamWaitEvent(e->gen_stream, e->gen_ev[0], 0));
-        }
-        HIPCHK(launch_tick_slow(e->R, int(e->cfg.semantics), e->P, T0, first_tick, win_first, t + int64_t(d),
-                                stats ? e->hist : nullptr, e->work[par], e->work_tick[par], cnt, nullptr,
-                                e->lane_general, e->gen_stream));
-        HIPCHK(hipEventRecord(e->gen_ev[1], e->gen_stream));
-        e->gen_pending = true;
-        e->gen_parity = par;
-        e->gen_w0 = stats_first;
-        e->gen_w1 = i;
-        e->gen_join = i + d;
-        e->gen_top = i + d;
-        e->gen_stats = stats;
-        ++e->n_general;
-      } else if (!skip_list) {
-        if (pp) {   // everything on list_stream (list(t) or list(t-1), a window join) before the engine stream
-          HIPCHK(hipEventRecord(e->ev_pp, e->list_stream));
-          HIPCHK(hipStreamWaitEvent(e->stream, e->ev_pp, 0));
-        } else if (pipe) {
-          HIPCHK(hipStreamWaitEvent(e->stream, e->ev_list[i & 3], 0));
-        }
-        HIPCHK(launch_tick_slow(e->R, int(e->cfg.semantics), e->P, T0, first_tick, win_first, t,
-                                stats ? e->hist : nullptr, e->work[par], e->work_tick[par], cnt, nullptr,
-                                e->lane_general, e->stream));
-        HIPCHK(launch_window_tail(e->P, e->work[par], e->wcount, par, e->stream));
-        ++e->n_general;
-      }
-      ++e->wpar;
-      // per-tick records: reduced (and all-reduced) per window — an overlapped
-      // window's once its general kernel has joined; with the list skipped
-      // nothing overlaps them, so one reduce (and one all-reduce) at the end of
-      // the call covers every tick (with a communicator too: a per-window
-      // flush costs the split tick a cross-stream join each, 418-424 vs
-      // 366-374 us per 20-tick call, round 4). The last one carries the check
-      // record.
-      CallCheck chk{e->wcount, par, skip_list ? 1 : 0, e->tstat + size_t(nticks) * NSTAT, int((e->lpar + 2) % 3),
-                    nullptr, nullptr, nullptr, 0u};
-      // the call's only reduce (every record in this launch), no communicator:
-      // the records also go straight to the host (CallCheck::hout)
-      e->mirror = stats && last && two && stats_first == 0 && !e->comm;
-      if (e->mirror) {
-        chk.hout = e->hrb;
-        chk.hdone = e->hdone;
-        chk.ctr = e->dctr;
-        chk.seq = ++e->seq;
-      }
-      const bool wflush = !skip_list || last;
-      if (stats && !overlap && wflush) {
-        if (int rc = join_half()) return rc;
-        // profile mode 1: the span of the call's launches ends with both
-        // halves, before the reduce (raftstep.h)
-        if (last && split && prof_b) {
-          HIPCHK(hipEventRecord(prof_b, e->stream));
-          prof_b = nullptr;
-        }
-        if (int rc = flush_window_stats(e, stats_first, i, (last && two) ? &chk : nullptr, nullptr, last)) return rc;
-      }
-      if (wflush) stats_first = i + 1;
-      win_first = t + 1;
-    }
+    if (!rc) rc = join_due_general(e, p, i);
+    if (!rc && ((i + 1) % e->slow_every == 0 || i + 1 == p.nticks)) rc = end_window(e, p, cs, k);
+    if (rc) return rc;
   }
-  if (int rc = join_half()) return rc;   // (the check record and the readback come after both halves)
-  if (split && prof_b) HIPCHK(hipEventRecord(prof_b, e->stream));   // the span ends with both halves
+  return RAFT_OK;
+}
+
+// After the last tick: joins, done flags, a stats-less skipping call's check record.
+static int tick_finish(raft_engine* e, const CallPlan& p, CallState& cs) {
+  if (int rc = join_half(e, p, cs)) return rc;   // (the check record and the readback come after both halves)
   e->hist_dirty = 0;   // every reduce of the call is issued
-  if (e->P.vx) e->vx_tick = first_tick + int64_t(nticks);
+  if (e->P.vx) e->vx_tick = p.first_tick + int64_t(p.nticks);
   e->sh_done = true;
   e->run_done = true;
   e->phase_done = true;
@@ -1605,7 +1686,7 @@ static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool s
     HIPCHK(hipStreamWaitEvent(e->stream, e->comm_ev[1], 0));
     e->comm_side = false;
   }
-  if (!stats && skip_list) {
+  if (!p.stats && p.skip_list) {
     // no readback in this call: the check record goes to tstat[cap + 1] and
     // its pinned copy is verified by the next call (settle_check)
     const CallCheck chk{e->wcount, int((e->wpar + NWORK - 1) % NWORK), 1, e->tstat + size_t(e->hist_cap + 1) * NSTAT,
@@ -1618,22 +1699,42 @@ static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool s
     e->pend_chk = true;
   }
   if (e->prof == 2) {
-    HIPCHK(hipEventRecord(rb, e->stream));
-    e->prof_n += nticks;
+    HIPCHK(hipEventRecord(cs.rb, e->stream));
+    e->prof_n += p.nticks;
   }
   if (e->P.dbg && e->diag_print) {   // diagnostics: lane classes summed over this call's ticks (synchronising)
     unsigned long long d[64];
     HIPCHK(hipMemcpyAsync(d, e->P.dbg, sizeof d, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemsetAsync(e->P.dbg, 0, sizeof d, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    fprintf(stderr, "raftstep: ticks %lld..%lld lean:", (long long)first_tick, (long long)(first_tick + nticks - 1));
-    for (int k = 0; k < 64; ++k) {
-      if (k == 32) fprintf(stderr, " | list:");
-      if (d[k]) fprintf(stderr, " %d=%llu", k & 31, d[k]);
+    fprintf(stderr, "raftstep: ticks %lld..%lld lean:", (long long)p.first_tick,
+            (long long)(p.first_tick + p.nticks - 1));
+    for (int j = 0; j < 64; ++j) {
+      if (j == 32) fprintf(stderr, " | list:");
+      if (d[j]) fprintf(stderr, " %d=%llu", j & 31, d[j]);
     }
     fprintf(stderr, "\n");
   }
   return RAFT_OK;
+}
+
+static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool stats) {
+  if (int rc = tick_begin(e, first_tick, nticks, stats)) return rc;
+  if (!nticks) return RAFT_OK;
+  const CallPlan p = plan_call(e, first_tick, nticks, stats);
+  // the plan's side effects: the running call's records, the host counters (raft_diag_read)
+  e->skipped_list = p.skip_list;
+  e->call_t0 = first_tick;
+  e->call_lean = p.call_lean;
+  e->n_ticks += nticks;
+  if (p.skip_list) e->n_skip_ticks += nticks;
+  if (p.steady) e->n_steady_ticks += nticks;
+  if (e->debug_pipe)
+    fprintf(stderr, "raftstep: ticks %lld..%lld pipeline %d\n", (long long)first_tick,
+            (long long)(first_tick + nticks - 1), int(p.pipe));
+  CallState cs{first_tick};
+  if (int rc = tick_issue(e, p, cs)) return rc;
+  return tick_finish(e, p, cs);
 }
 
 // Waits for the engine stream. With a communicator the wait is bounded by
@@ -1818,8 +1919,7 @@ int raft_append_entries_batch(raft_engine* e, int64_t now_tick, const raft_ae_re
   if (!e || (n && (!reqs || !out))) return fail(RAFT_EINVAL, "null argument");
   if (int rc = settle_check(e)) return rc;
   if (int rc = ring_flush(e)) return rc;
-  e->run_valid = false;   // host mutation: entries from here on are not the trace's
-  e->steady_origin = e->steady_ok = e->phase_ok = false;   // host mutation (the list skip needs a fresh proof)
+  host_mutation(e);
   if (n == 0) return RAFT_OK;
   if (int rc = check_distinct(e, &reqs[0].group, sizeof(raft_ae_req), n)) return rc;
   std::vector<DevOp> ops(n);
@@ -1873,8 +1973,7 @@ int raft_request_vote_batch(raft_engine* e, int64_t now_tick, const raft_vote_re
   if (!e || (n && (!reqs || !out))) return fail(RAFT_EINVAL, "null argument");
   if (int rc = settle_check(e)) return rc;
   if (int rc = ring_flush(e)) return rc;
-  e->run_valid = false;   // host mutation: entries from here on are not the trace's
-  e->steady_origin = e->steady_ok = e->phase_ok = false;   // host mutation (the list skip needs a fresh proof)
+  host_mutation(e);
   if (n == 0) return RAFT_OK;
   if (int rc = check_distinct(e, &reqs[0].group, sizeof(raft_vote_req), n)) return rc;
   std::vector<DevOp> ops(n);
@@ -1906,8 +2005,7 @@ int raft_group_ops_batch(raft_engine* e, int64_t now_tick, const raft_group_op* 
   if (!e || (n && (!ops_in || !out))) return fail(RAFT_EINVAL, "null argument");
   if (int rc = settle_check(e)) return rc;
   if (int rc = ring_flush(e)) return rc;
-  e->run_valid = false;   // host mutation: entries from here on are not the trace's
-  e->steady_origin = e->steady_ok = e->phase_ok = false;   // host mutation (the list skip needs a fresh proof)
+  host_mutation(e);
   if (n == 0) return RAFT_OK;
   if (int rc = check_distinct(e, &ops_in[0].group, sizeof(raft_group_op), n)) return rc;
   std::vector<DevOp> ops(n);

@@ -2449,74 +2449,60 @@ __global__ __launch_bounds__(256) void tick_fused_kernel(DevPlanes P, Trace T, i
   }
 }
 
-template <int R, bool CRC, int SEM>
-static void launch_fused_t(const DevPlanes& P, const Trace& T, int nt, unsigned long long* stats, uint32_t* list,
-                           uint32_t* count, hipStream_t s, hipEvent_t a, hipEvent_t b) {
-  hipExtLaunchKernelGGL(tick_fused_kernel<R, CRC, SEM>, grid_for(P.G), dim3(256), 0, s, a, b, 0, P, T, nt, stats,
-                        list, count);
-}
-hipError_t launch_tick_fused(int R, int sem, const DevPlanes& P, const Trace& T, int nticks, unsigned long long* stats,
-                             uint32_t* list, uint32_t* count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
-  const bool crc = P.crc_on != 0;
-#define RAFT_FUSED(CRC_)                                                                                        \
-  if (sem == SEM_RAFT) {                                                                                         \
-    RAFT_DISPATCH_R(R, (launch_fused_t<RR, CRC_, SEM_RAFT>(P, T, nticks, stats, list, count, s, ev_start, ev_stop))) \
-  } else {                                                                                                       \
-    RAFT_DISPATCH_R(R, (launch_fused_t<RR, CRC_, SEM_REF>(P, T, nticks, stats, list, count, s, ev_start, ev_stop)))  \
-  }
-  if (crc) { RAFT_FUSED(true); } else { RAFT_FUSED(false); }
-#undef RAFT_FUSED
-  return hipGetLastError();
+// (R, sem, crc) as template arguments: f(R, CRC, SEM) is called once with
+// integral-constant tags (all R x CRC x SEM instantiations of what f launches)
+template <class F>
+static hipError_t dispatch_tick(int R, int sem, bool crc, F f) {
+  auto with = [&](auto CRC, auto SEM) -> hipError_t {
+    RAFT_DISPATCH_R(R, (f(std::integral_constant<int, RR>{}, CRC, SEM)))
+    return hipGetLastError();
+  };
+  using Raft = std::integral_constant<int, SEM_RAFT>;
+  using Ref = std::integral_constant<int, SEM_REF>;
+  if (crc) return sem == SEM_RAFT ? with(std::true_type{}, Raft{}) : with(std::true_type{}, Ref{});
+  return sem == SEM_RAFT ? with(std::false_type{}, Raft{}) : with(std::false_type{}, Ref{});
 }
 
-template <int R, bool CRC, int SEM>
-static void launch_fast_t(const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
-                          int32_t* work_tick, uint32_t* work_count, int force_slow, hipStream_t s, hipEvent_t a,
-                          hipEvent_t b) {
-  hipExtLaunchKernelGGL(tick_fast_kernel<R, CRC, SEM>, grid_for(P.G), dim3(256), 0, s, a, b, 0, P, T, stats, work,
-                        work_tick, work_count, force_slow);
+hipError_t launch_tick_fused(int R, int sem, const DevPlanes& P, const Trace& T, int nticks, unsigned long long* stats,
+                             uint32_t* list, uint32_t* count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+  return dispatch_tick(R, sem, P.crc_on != 0, [&](auto r, auto crc, auto sm) {
+    hipExtLaunchKernelGGL((tick_fused_kernel<r(), crc(), sm()>), grid_for(P.G), dim3(256), 0, s, ev_start, ev_stop, 0,
+                          P, T, nticks, stats, list, count);
+  });
 }
 hipError_t launch_tick_fast(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
                             int32_t* work_tick, uint32_t* work_count, int force_slow, hipStream_t s,
                             hipEvent_t ev_start, hipEvent_t ev_stop) {
-  const bool crc = P.crc_on != 0;
-#define RAFT_FAST(CRC_)                                                                                            \
-  if (sem == SEM_RAFT) {                                                                                           \
-    RAFT_DISPATCH_R(R, (launch_fast_t<RR, CRC_, SEM_RAFT>(P, T, stats, work, work_tick, work_count, force_slow, s, \
-                                                          ev_start, ev_stop)))                                     \
-  } else {                                                                                                         \
-    RAFT_DISPATCH_R(R, (launch_fast_t<RR, CRC_, SEM_REF>(P, T, stats, work, work_tick, work_count, force_slow, s,  \
-                                                         ev_start, ev_stop)))                                      \
-  }
-  if (crc) { RAFT_FAST(true); } else { RAFT_FAST(false); }
-#undef RAFT_FAST
-  return hipGetLastError();
+  return dispatch_tick(R, sem, P.crc_on != 0, [&](auto r, auto crc, auto sm) {
+    hipExtLaunchKernelGGL((tick_fast_kernel<r(), crc(), sm()>), grid_for(P.G), dim3(256), 0, s, ev_start, ev_stop, 0,
+                          P, T, stats, work, work_tick, work_count, force_slow);
+  });
 }
 
-template <int R, bool CRC, int SEM>
-static void launch_lean_t(const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* list,
-                          uint32_t* count, int lflags, hipStream_t s, hipEvent_t a, hipEvent_t b, uint64_t g0 = 0,
-                          uint64_t ng = ~0ull, uint32_t* zc = nullptr, bool steady = false) {
-  const uint64_t n = std::min<uint64_t>(ng, P.G - g0);
-  if (steady) {   // (the engine's gate: list skipped, no device counters, every live group in phase)
-    const SteadyPlanes SP = steady_planes(P);
-    const SteadyTick ST = steady_tick_args(P, T);
-    if (P.sh)
-      hipExtLaunchKernelGGL((tick_lean_kernel<R, CRC, SEM, true, true>), grid_for(n), dim3(256), 0, s, a, b, 0, SP, ST,
-                            stats, list, count, 0, uint32_t(g0), static_cast<uint32_t*>(nullptr));
-    else
-      hipExtLaunchKernelGGL((tick_lean_kernel<R, CRC, SEM, true, false>), grid_for(n), dim3(256), 0, s, a, b, 0, SP, ST,
-                            stats, list, count, 0, uint32_t(g0), static_cast<uint32_t*>(nullptr));
-    return;
-  }
-  hipExtLaunchKernelGGL(tick_lean_kernel<R, CRC, SEM>, grid_for(n), dim3(256), 0, s, a, b, 0, P, T, stats, list,
-                        count, lflags, uint32_t(g0), zc);
+hipError_t launch_tick_lean(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* list,
+                            uint32_t* count, int lflags, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
+                            uint64_t g0, uint64_t ng, uint32_t* zero_count, bool steady) {
+  const dim3 grid = grid_for(std::min<uint64_t>(ng, P.G - g0));
+  return dispatch_tick(R, sem, P.crc_on != 0, [&](auto r, auto crc, auto sm) {
+    if (steady) {   // (the engine's gate: list skipped, no device counters, every live group in phase)
+      const SteadyPlanes SP = steady_planes(P);
+      const SteadyTick ST = steady_tick_args(P, T);
+      if (P.sh)
+        hipExtLaunchKernelGGL((tick_lean_kernel<r(), crc(), sm(), true, true>), grid, dim3(256), 0, s, ev_start, ev_stop,
+                              0, SP, ST, stats, list, count, 0, uint32_t(g0), static_cast<uint32_t*>(nullptr));
+      else
+        hipExtLaunchKernelGGL((tick_lean_kernel<r(), crc(), sm(), true, false>), grid, dim3(256), 0, s, ev_start, ev_stop,
+                              0, SP, ST, stats, list, count, 0, uint32_t(g0), static_cast<uint32_t*>(nullptr));
+      return;
+    }
+    hipExtLaunchKernelGGL((tick_lean_kernel<r(), crc(), sm()>), grid, dim3(256), 0, s, ev_start, ev_stop, 0, P, T, stats,
+                          list, count, lflags, uint32_t(g0), zero_count);
+  });
 }
-
-template <int R, bool CRC, int SEM>
-static void launch_list_t(const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
-                          int32_t* work_tick, uint32_t* work_count, uint32_t* list, uint32_t* count,
-                          uint32_t* next_count, const ListNext* next, hipStream_t s, hipEvent_t c, hipEvent_t d) {
+hipError_t launch_tick_list(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
+                            int32_t* work_tick, uint32_t* work_count, uint32_t* list, uint32_t* count,
+                            uint32_t* next_count, const ListNext* next, hipStream_t s, hipEvent_t ev_start,
+                            hipEvent_t ev_stop) {
   const int steps = next ? 2 : 1;
   const ListNext nx = next ? *next : ListNext{nullptr, nullptr, nullptr, nullptr};
   // blocks of four waves, a resident grid striding over the list (one-wave
@@ -2527,73 +2513,13 @@ static void launch_list_t(const DevPlanes& P, const Trace& T, unsigned long long
     const char* v = std::getenv("RAFTSTEP_LIST_BLOCKS");   // experiment knob: cap the resident grid
     return v ? unsigned(std::strtoul(v, nullptr, 10)) : 0u;
   }();
-  uint64_t lim = resident_blocks(tick_list_kernel<R, CRC, SEM, 256>, 256);
-  if (cap) lim = std::min<uint64_t>(lim, cap);
-  const unsigned blocks = unsigned(std::min<uint64_t>((P.G + GPB - 1) / GPB, lim));
-  hipExtLaunchKernelGGL(tick_list_kernel<R, CRC, SEM, 256>, dim3(blocks), dim3(256), 0, s, c, d, 0, P, T, stats, work,
-                        work_tick, work_count, list, count, next_count, steps, nx);
-}
-
-template <int R, bool CRC, int SEM>
-static void launch_two_pass_t(const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
-                              int32_t* work_tick, uint32_t* work_count, uint32_t* list, uint32_t* count,
-                              uint32_t* next_count, hipStream_t s, hipEvent_t a, hipEvent_t b, hipEvent_t c,
-                              hipEvent_t d, bool skip_list) {
-  launch_lean_t<R, CRC, SEM>(P, T, stats, list, count, 0, s, a, b);
-  if (skip_list) return;   // the engine proved the list empty (engine.cpp, steady-state list skip)
-  launch_list_t<R, CRC, SEM>(P, T, stats, work, work_tick, work_count, list, count, next_count, nullptr, s, c, d);
-}
-hipError_t launch_tick_two_pass(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats,
-                                uint32_t* work, int32_t* work_tick, uint32_t* work_count, uint32_t* list,
-                                uint32_t* count, uint32_t* next_count, hipStream_t s, hipEvent_t lean_start,
-                                hipEvent_t lean_stop, hipEvent_t list_start, hipEvent_t list_stop, bool skip_list) {
-  const bool crc = P.crc_on != 0;
-#define RAFT_TWO(CRC_)                                                                                            \
-  if (sem == SEM_RAFT) {                                                                                           \
-    RAFT_DISPATCH_R(R, (launch_two_pass_t<RR, CRC_, SEM_RAFT>(P, T, stats, work, work_tick, work_count, list, count, \
-                                                              next_count, s, lean_start, lean_stop, list_start,      \
-                                                              list_stop, skip_list)))                                \
-  } else {                                                                                                         \
-    RAFT_DISPATCH_R(R, (launch_two_pass_t<RR, CRC_, SEM_REF>(P, T, stats, work, work_tick, work_count, list, count,  \
-                                                             next_count, s, lean_start, lean_stop, list_start,       \
-                                                             list_stop, skip_list)))                                 \
-  }
-  if (crc) { RAFT_TWO(true); } else { RAFT_TWO(false); }
-#undef RAFT_TWO
-  return hipGetLastError();
-}
-hipError_t launch_tick_lean(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* list,
-                            uint32_t* count, int lflags, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
-                            uint64_t g0, uint64_t ng, uint32_t* zero_count, bool steady) {
-  const bool crc = P.crc_on != 0;
-#define RAFT_LEAN(CRC_)                                                                                          \
-  if (sem == SEM_RAFT) {                                                                                          \
-    RAFT_DISPATCH_R(R, (launch_lean_t<RR, CRC_, SEM_RAFT>(P, T, stats, list, count, lflags, s, ev_start, ev_stop,   \
-                                                          g0, ng, zero_count, steady)))                           \
-  } else {                                                                                                        \
-    RAFT_DISPATCH_R(R, (launch_lean_t<RR, CRC_, SEM_REF>(P, T, stats, list, count, lflags, s, ev_start, ev_stop,    \
-                                                         g0, ng, zero_count, steady)))                            \
-  }
-  if (crc) { RAFT_LEAN(true); } else { RAFT_LEAN(false); }
-#undef RAFT_LEAN
-  return hipGetLastError();
-}
-hipError_t launch_tick_list(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
-                            int32_t* work_tick, uint32_t* work_count, uint32_t* list, uint32_t* count,
-                            uint32_t* next_count, const ListNext* next, hipStream_t s, hipEvent_t ev_start,
-                            hipEvent_t ev_stop) {
-  const bool crc = P.crc_on != 0;
-#define RAFT_LIST(CRC_)                                                                                          \
-  if (sem == SEM_RAFT) {                                                                                          \
-    RAFT_DISPATCH_R(R, (launch_list_t<RR, CRC_, SEM_RAFT>(P, T, stats, work, work_tick, work_count, list, count,   \
-                                                          next_count, next, s, ev_start, ev_stop)))                \
-  } else {                                                                                                        \
-    RAFT_DISPATCH_R(R, (launch_list_t<RR, CRC_, SEM_REF>(P, T, stats, work, work_tick, work_count, list, count,    \
-                                                         next_count, next, s, ev_start, ev_stop)))                 \
-  }
-  if (crc) { RAFT_LIST(true); } else { RAFT_LIST(false); }
-#undef RAFT_LIST
-  return hipGetLastError();
+  return dispatch_tick(R, sem, P.crc_on != 0, [&](auto r, auto crc, auto sm) {
+    uint64_t lim = resident_blocks(tick_list_kernel<r(), crc(), sm(), 256>, 256);
+    if (cap) lim = std::min<uint64_t>(lim, cap);
+    const unsigned blocks = unsigned(std::min<uint64_t>((P.G + GPB - 1) / GPB, lim));
+    hipExtLaunchKernelGGL((tick_list_kernel<r(), crc(), sm(), 256>), dim3(blocks), dim3(256), 0, s, ev_start, ev_stop, 0,
+                          P, T, stats, work, work_tick, work_count, list, count, next_count, steps, nx);
+  });
 }
 
 }  // namespace raftstep

@@ -43,20 +43,18 @@ struct DevRes {
 hipError_t launch_tick_fast(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
                             int32_t* work_tick, uint32_t* work_count, int force_slow, hipStream_t s,
                             hipEvent_t ev_start, hipEvent_t ev_stop);
-// Two-pass tick: tick_lean_kernel takes the compressed steady groups and
-// appends every other live group to `list` (counter `count`), then
-// tick_list_kernel runs the full fast_group over that list and zeroes
-// `next_count`. Events (may be null) time each dispatch.
-hipError_t launch_tick_two_pass(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats,
-                                uint32_t* work, int32_t* work_tick, uint32_t* work_count, uint32_t* list,
-                                uint32_t* count, uint32_t* next_count, hipStream_t s, hipEvent_t lean_start,
-                                hipEvent_t lean_stop, hipEvent_t list_start, hipEvent_t list_stop, bool skip_list);
-// The two passes launched separately (the pipelined tick, engine.cpp):
+// Two-pass tick: tick_lean_kernel (launch_tick_lean) takes the compressed
+// steady groups and appends every other live group to `list` (counter
+// `count`), then tick_list_kernel (launch_tick_list) runs the full fast_group
+// over that list and zeroes `next_count`. Events (may be null) time each
+// dispatch. A list-skipping call launches the lean kernel alone; the in-line
+// and the pipelined tick launch both (engine.cpp tick_skip / tick_inline /
+// tick_pipelined).
 // lflags bit 0 = leave the groups marked in P.glst alone (and clear the
-// marks), bit 1 = mark the groups passed on. With `next` the list kernel
-// runs its groups through the following tick too (a second fast_group step
-// on the staged state; its stats and deferrals go to next's record and
-// worklist), so that the next lean kernel can run beside it.
+// marks), bit 1 = mark the groups passed on (both the pipelined tick's). With
+// `next` the list kernel runs its groups through the following tick too (a
+// second fast_group step on the staged state; its stats and deferrals go to
+// next's record and worklist), so that the next lean kernel can run beside it.
 struct ListNext {
   unsigned long long* stats;    // the following tick's stats slots
   uint32_t* work;               // the worklist of the following tick's window

@@ -201,6 +201,38 @@ def random_state(rng, G, R, K, max_term=6, max_log=12):
     return st
 
 
+def staged_values(seed, t, n, E, groups):
+    """Staged client values of ticks [t, t+n): any int64 >= 0, a function of the tick."""
+    return np.random.default_rng([seed, t]).integers(0, 1 << 62, size=(n, E, groups), dtype=np.int64)
+
+
+def apply_op(impl, op, t, cfg_kw, **tick_kw):
+    """One state-changing operation of a tests/steady_model.py schedule on
+    `impl` (engine or oracle) at running tick t: ticks (client values staged
+    first where the config stages them), zero-tick calls, gaps, init_steady and
+    handler batches; tick_kw goes to impl.tick (the oracle's threads). Returns
+    (the next tick, the call's result or None)."""
+    import steady_model as M
+    kind = op[0]
+    if kind in ("tick", "tick0"):
+        k, stats = (op[1], op[2]) if kind == "tick" else (0, op[1])
+        if k and impl.cfg.client_source == abi.CLIENT_STAGED:
+            impl.stage_values(t, staged_values(int(impl.cfg.seed), t, k, impl.cfg.entries_per_tick, impl.cfg.groups))
+        return t + k, impl.tick(t, k, stats=stats, **tick_kw)
+    if kind == "gap":
+        return t + op[1], None
+    if kind == "init_steady":
+        impl.init_steady(op[1], op[2])
+        return op[2] + 1, None
+    items = M.batch_items(kind, op[1], cfg_kw)
+    if kind == "append_entries":
+        return t, impl.append_entries(t, *ae_reqs(items))
+    if kind == "request_vote":
+        return t, impl.request_vote(t, vote_reqs(items))
+    assert kind == "group_ops", kind
+    return t, impl.group_ops(t, ops(items))
+
+
 def random_events(impl, rng, n_events, t0=0):
     """Drive `impl` (engine, oracle or a trace.TraceRecorder over one) through a
     random mix of tick ranges and handler batches; returns the next tick."""

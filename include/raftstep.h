@@ -412,8 +412,10 @@ enum raft_diag_counter {
   RAFT_DIAG_TICKS = 64,
   RAFT_DIAG_TICKS_LIST_SKIPPED = 65,  /* ticks run by the lean kernel alone (steady-state list skip) */
   RAFT_DIAG_GENERAL_LAUNCHES = 66,
-  RAFT_DIAG_TICKS_STEADY_FORM = 67    /* ... of those, ticks the lean kernel ran in its steady form (every live group
+  RAFT_DIAG_TICKS_STEADY_FORM = 67,   /* ... of those, ticks the lean kernel ran in its steady form (every live group
                                          proven in the global ring phase; RAFTSTEP_STEADY_FORM=0: never) */
+  RAFT_DIAG_LAUNCHES_STEADY_ONE = 68, /* steady-form launches that ran the one-entry instantiation (a split tick: two) */
+  RAFT_DIAG_TICKS_SPLIT = 69          /* list-skipping ticks issued as two halves on two streams */
 };
 int raft_diag_enable(raft_engine* e, int on);
 int raft_diag_read(raft_engine* e, uint64_t* counters, uint32_t n);

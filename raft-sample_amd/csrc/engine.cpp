@@ -212,9 +212,18 @@ struct raft_engine {
   // two streams, so that one half's kernel boundary (drain, launch, the
   // previous kernel's tail) overlaps the other half's streaming. Groups never
   // address each other, so the halves are independent; they join before every
-  // statistics reduce and at the end of the call. RAFTSTEP_SPLIT_STEADY=0:
-  // one launch per tick (exact either way: tests/test_gpu_engine_checks.py).
-  int split_steady = 1;
+  // statistics reduce and at the end of the call. The fork and the join are
+  // cross-stream waits, a fixed cost per call, while the overlap pays per
+  // tick and grows with a wave's life (the drain it hides): with the lean
+  // kernel's steady form, one entry per tick and no payload CRC, a call of
+  // fewer than SPLIT_MIN_TICKS ticks is one launch per tick (plan_call;
+  // measured: profiles/r09/single/ — C2, C2X, C2S; C5, 64 entries with CRC,
+  // is 3% faster in halves at 20 ticks per call and keeps them, as does every
+  // shape not measured). RAFTSTEP_SPLIT_STEADY=0 / 1 force one launch per
+  // tick / the two halves whatever the call (exact either way:
+  // tests/test_gpu_engine_checks.py, tests/test_gpu_steady_single.py).
+  int split_steady = -1;   // (-1: the default above; the general body always splits)
+  static constexpr uint32_t SPLIT_MIN_TICKS = 48;
   hipStream_t half_stream = nullptr;
   hipEvent_t ev_half[2] = {nullptr, nullptr};   // engine -> half stream, half stream -> engine
   hipEvent_t ev_lean[2] = {nullptr, nullptr};   // engine stream -> list_stream (list(t) after lean(t))
@@ -244,6 +253,9 @@ struct raft_engine {
   // RAFTSTEP_STEADY_FORM=0: the general body everywhere (exact either way:
   // tests/test_gpu_steady_form.py).
   int steady_form = 1;
+  // RAFTSTEP_ISSUE_TIME=1: one stderr line per call of 8 ticks or more with the
+  // host time its launches took to issue (tick_issue; profiles/r09/single/)
+  int issue_time = 0;
   bool phase_ok = false, phase_done = false;   // (phase_done: the last call issued everything)
   int64_t phase_next = 0;       // the tick the next call must start at
   // A skipping call without statistics ends with the check record written to
@@ -259,7 +271,7 @@ struct raft_engine {
   // diagnostics: lane class counters on the device (raft_diag_enable), host counters
   int diag_print = 0;
   unsigned long long* dbg_buf = nullptr;   // the device counters (P.dbg while counting)           // RAFTSTEP_DEBUG_FAST: print the class counters after every call (synchronising)
-  uint64_t n_ticks = 0, n_skip_ticks = 0, n_general = 0, n_steady_ticks = 0;
+  uint64_t n_ticks = 0, n_skip_ticks = 0, n_general = 0, n_steady_ticks = 0, n_one_launches = 0, n_split_ticks = 0;
   // handler-batch staging
   void* stage = nullptr;
   size_t stage_cap = 0;
@@ -766,6 +778,7 @@ int raft_engine_create(const raft_config* cfg, raft_engine** out) {
   e->P.diag = diag_lean;
   if (const char* sp = getenv("RAFTSTEP_SPLIT_STEADY")) e->split_steady = atoi(sp) != 0;
   if (const char* sf = getenv("RAFTSTEP_STEADY_FORM")) e->steady_form = atoi(sf) != 0;
+  if (const char* it = getenv("RAFTSTEP_ISSUE_TIME")) e->issue_time = atoi(it) != 0;
 
   // (the depths the oracle tests cover: 0..3, tests/test_gpu_pipeline.py)
   if (const char* og = getenv("RAFTSTEP_OVERLAP_GENERAL")) e->overlap_general = std::min(3, std::max(0, atoi(og)));
@@ -1272,6 +1285,7 @@ struct CallPlan {
   uint64_t Gs, half; // split steady tick: the groups, and those of the engine stream's half
   bool steady, split;   // the lean kernel's steady form (raft_engine::steady_form); split steady tick (split_steady)
   TickMode mode;
+  SteadyCall sc;        // steady: the form's instantiations and planes' record, resolved once (tick_impl)
 };
 
 static CallPlan plan_call(const raft_engine* e, int64_t first_tick, uint32_t nticks, bool stats) {
@@ -1297,7 +1311,11 @@ static CallPlan plan_call(const raft_engine* e, int64_t first_tick, uint32_t nti
   // counters and timing diagnostics keep the general body, and so does the
   // shared ring in slot chunks (it needs corruption configured: no list skip)
   p.steady = lean_alone && e->steady_form && e->phase_ok && !e->P.dbg && !e->P.diag && e->P.sh_cs == 0;
-  p.split = lean_alone && e->split_steady && p.half >= 65536 && p.Gs - p.half >= 65536;
+  // (short waves: the shapes measured faster in one launch at short calls, see raft_engine::split_steady)
+  const bool short_waves = e->cfg.entries_per_tick == 1 && !e->cfg.payload_crc;
+  const bool want_split = e->split_steady >= 0 ? e->split_steady != 0
+                                               : !p.steady || !short_waves || nticks >= raft_engine::SPLIT_MIN_TICKS;
+  p.split = lean_alone && want_split && p.half >= 65536 && p.Gs - p.half >= 65536;
   p.mode = p.fuse > 1 ? TickMode::Fused : p.pipe ? TickMode::Pipelined : !p.two ? TickMode::Fast
            : p.skip_list ? TickMode::Skip : TickMode::Inline;
   return p;
@@ -1508,13 +1526,21 @@ static int tick_inline(raft_engine* e, const Tick& k) {
 static int tick_skip(raft_engine* e, const CallPlan& p, CallState& cs, const Tick& k) {
   const uint32_t L = e->lpar % 3;
   const int sem = int(e->cfg.semantics);
-  HIPCHK(launch_tick_lean(e->R, sem, e->P, k.T, k.st, e->blist[L], lcount(e, L), 0, e->stream, k.a,
-                          p.split ? nullptr : k.b, 0, p.split ? p.half : ~0ull, nullptr, p.steady));
-  if (p.split) {
-    HIPCHK(launch_tick_lean(e->R, sem, e->P, k.T, k.st, e->blist[L], lcount(e, L), 0, e->half_stream, nullptr,
-                            nullptr, p.half, p.Gs - p.half, nullptr, p.steady));
-    cs.half_busy = true;
+  const uint64_t n0 = p.split ? p.half : ~0ull;   // the engine stream's groups
+  if (p.steady) {
+    HIPCHK(launch_tick_steady(p.sc, k.T, k.st, e->blist[L], lcount(e, L), e->stream, k.a, p.split ? nullptr : k.b, 0, n0,
+                              &e->n_one_launches));
+    if (p.split)
+      HIPCHK(launch_tick_steady(p.sc, k.T, k.st, e->blist[L], lcount(e, L), e->half_stream, nullptr, nullptr, p.half,
+                                p.Gs - p.half, &e->n_one_launches));
+  } else {
+    HIPCHK(launch_tick_lean(e->R, sem, e->P, k.T, k.st, e->blist[L], lcount(e, L), 0, e->stream, k.a,
+                            p.split ? nullptr : k.b, 0, n0));
+    if (p.split)
+      HIPCHK(launch_tick_lean(e->R, sem, e->P, k.T, k.st, e->blist[L], lcount(e, L), 0, e->half_stream, nullptr,
+                              nullptr, p.half, p.Gs - p.half));
   }
+  if (p.split) cs.half_busy = true;
   ++e->lpar;
   return RAFT_OK;
 }
@@ -1719,9 +1745,14 @@ static int tick_finish(raft_engine* e, const CallPlan& p, CallState& cs) {
 }
 
 static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool stats) {
+  // RAFTSTEP_ISSUE_TIME: host time before the first launch (tick_begin, the plan) and of the launches
+  const bool timed = e->issue_time && nticks >= 8;
+  const auto clk = [timed] { return timed ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point{}; };
+  const auto tb = clk();
   if (int rc = tick_begin(e, first_tick, nticks, stats)) return rc;
   if (!nticks) return RAFT_OK;
-  const CallPlan p = plan_call(e, first_tick, nticks, stats);
+  CallPlan p = plan_call(e, first_tick, nticks, stats);
+  if (p.steady) HIPCHK(steady_resolve(e->R, int(e->cfg.semantics), e->P, &p.sc));
   // the plan's side effects: the running call's records, the host counters (raft_diag_read)
   e->skipped_list = p.skip_list;
   e->call_t0 = first_tick;
@@ -1729,11 +1760,21 @@ static int tick_impl(raft_engine* e, int64_t first_tick, uint32_t nticks, bool s
   e->n_ticks += nticks;
   if (p.skip_list) e->n_skip_ticks += nticks;
   if (p.steady) e->n_steady_ticks += nticks;
+  if (p.mode == TickMode::Skip && p.split) e->n_split_ticks += nticks;
   if (e->debug_pipe)
     fprintf(stderr, "raftstep: ticks %lld..%lld pipeline %d\n", (long long)first_tick,
             (long long)(first_tick + nticks - 1), int(p.pipe));
   CallState cs{first_tick};
+  const auto t0 = clk();
   if (int rc = tick_issue(e, p, cs)) return rc;
+  if (timed) {
+    const auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    const double ui = us(t0, clk());
+    const uint32_t launches = nticks * (p.mode == TickMode::Skip && p.split ? 2u : 1u);
+    fprintf(stderr, "raftstep: issue ticks %u mode %d steady %d split %d: before the first launch %.1f us, launches "
+            "%.1f us, %.2f us per tick, %.2f us per launch\n", nticks, int(p.mode), int(p.steady), int(p.split),
+            us(tb, t0), ui, ui / nticks, ui / launches);
+  }
   return tick_finish(e, p, cs);
 }
 
@@ -2175,7 +2216,7 @@ int raft_diag_enable(raft_engine* e, int on) {
   }
   if (e->dbg_buf) HIPCHK(hipMemsetAsync(e->dbg_buf, 0, RAFT_DIAG_DEVICE_COUNTERS * 8, e->stream));
   e->P.dbg = on ? e->dbg_buf : nullptr;   // (the buffer stays allocated; counting stops)
-  e->n_ticks = e->n_skip_ticks = e->n_general = e->n_steady_ticks = 0;
+  e->n_ticks = e->n_skip_ticks = e->n_general = e->n_steady_ticks = e->n_one_launches = e->n_split_ticks = 0;
   HIPCHK(hipStreamSynchronize(e->stream));
   return RAFT_OK;
 }
@@ -2194,7 +2235,9 @@ int raft_diag_read(raft_engine* e, uint64_t* counters, uint32_t n) {
   all[RAFT_DIAG_TICKS_LIST_SKIPPED] = e->n_skip_ticks;
   all[RAFT_DIAG_GENERAL_LAUNCHES] = e->n_general;
   all[RAFT_DIAG_TICKS_STEADY_FORM] = e->n_steady_ticks;
-  e->n_ticks = e->n_skip_ticks = e->n_general = e->n_steady_ticks = 0;
+  all[RAFT_DIAG_LAUNCHES_STEADY_ONE] = e->n_one_launches;
+  all[RAFT_DIAG_TICKS_SPLIT] = e->n_split_ticks;
+  e->n_ticks = e->n_skip_ticks = e->n_general = e->n_steady_ticks = e->n_one_launches = e->n_split_ticks = 0;
   for (uint32_t i = 0; i < n; ++i) counters[i] = all[i];
   return RAFT_OK;
 }

@@ -2302,13 +2302,15 @@ __device__ __forceinline__ void lean_tick(const DevPlanes& P, const Trace& T, un
 // can prove every live group in the global ring phase (engine.cpp,
 // raft_engine::phase_ok; SH: the entries go to the shared ring). One kernel
 // name for both, so that profiles and the bench's kernel filters see the
-// headline's kernel whichever body it runs.
-template <int R, bool CRC, int SEM, bool STEADY = false, bool SH = false>
+// headline's kernel whichever body it runs. ONE: the steady form's
+// instantiation for a launch with one trace-RNG entry per group, plain record
+// stores and the shared ring (tick_steady.hpp).
+template <int R, bool CRC, int SEM, bool STEADY = false, bool SH = false, bool ONE = false>
 __global__ __launch_bounds__(256) void tick_lean_kernel(std::conditional_t<STEADY, SteadyPlanes, DevPlanes> P,
                                                         std::conditional_t<STEADY, SteadyTick, Trace> T,
                                                         unsigned long long* stats, uint32_t* list, uint32_t* count,
                                                         int lflags, uint32_t gofs, uint32_t* zc) {
-  if constexpr (STEADY) steady_tick<R, CRC, SEM == SEM_RAFT, SH>(P, T, stats, list, count, gofs);
+  if constexpr (STEADY) steady_tick<R, CRC, SEM == SEM_RAFT, SH, ONE>(P, T, stats, list, count, gofs);
   else lean_tick<R, CRC, SEM>(P, T, stats, list, count, lflags, gofs, zc);
 }
 
@@ -2481,23 +2483,44 @@ hipError_t launch_tick_fast(int R, int sem, const DevPlanes& P, const Trace& T, 
 
 hipError_t launch_tick_lean(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* list,
                             uint32_t* count, int lflags, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
-                            uint64_t g0, uint64_t ng, uint32_t* zero_count, bool steady) {
+                            uint64_t g0, uint64_t ng, uint32_t* zero_count) {
   const dim3 grid = grid_for(std::min<uint64_t>(ng, P.G - g0));
   return dispatch_tick(R, sem, P.crc_on != 0, [&](auto r, auto crc, auto sm) {
-    if (steady) {   // (the engine's gate: list skipped, no device counters, every live group in phase)
-      const SteadyPlanes SP = steady_planes(P);
-      const SteadyTick ST = steady_tick_args(P, T);
-      if (P.sh)
-        hipExtLaunchKernelGGL((tick_lean_kernel<r(), crc(), sm(), true, true>), grid, dim3(256), 0, s, ev_start, ev_stop,
-                              0, SP, ST, stats, list, count, 0, uint32_t(g0), static_cast<uint32_t*>(nullptr));
-      else
-        hipExtLaunchKernelGGL((tick_lean_kernel<r(), crc(), sm(), true, false>), grid, dim3(256), 0, s, ev_start, ev_stop,
-                              0, SP, ST, stats, list, count, 0, uint32_t(g0), static_cast<uint32_t*>(nullptr));
-      return;
-    }
     hipExtLaunchKernelGGL((tick_lean_kernel<r(), crc(), sm()>), grid, dim3(256), 0, s, ev_start, ev_stop, 0, P, T, stats,
                           list, count, lflags, uint32_t(g0), zero_count);
   });
+}
+
+// The steady form (the engine's gate: list skipped, no device counters, every
+// live group in phase). Once per call: the planes' record and the
+// instantiations, every one of the same signature.
+hipError_t steady_resolve(int R, int sem, const DevPlanes& P, SteadyCall* out) {
+  out->planes = steady_planes(P);
+  out->generic = out->one = nullptr;
+  out->cv = P.cv; out->cv_t0 = P.cv_t0; out->cv_tstride = P.cv_tstride;
+  return dispatch_tick(R, sem, P.crc_on != 0, [&](auto r, auto crc, auto sm) {
+    if (P.sh) {
+      out->generic = reinterpret_cast<const void*>(&tick_lean_kernel<r(), crc(), sm(), true, true, false>);
+      if (steady_one(out->planes, true))
+        out->one = reinterpret_cast<const void*>(&tick_lean_kernel<r(), crc(), sm(), true, true, true>);
+    } else {
+      out->generic = reinterpret_cast<const void*>(&tick_lean_kernel<r(), crc(), sm(), true, false, false>);
+    }
+  });
+}
+hipError_t launch_tick_steady(const SteadyCall& C, const Trace& T, unsigned long long* stats, uint32_t* list,
+                              uint32_t* count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, uint64_t g0,
+                              uint64_t ng, uint64_t* one_launches) {
+  SteadyTick ST = steady_tick_args(C, T);
+  const bool one = C.one && steady_one(ST);
+  if (one && one_launches) ++*one_launches;
+  uint32_t gofs = uint32_t(g0);
+  int lflags = 0;
+  uint32_t* zc = nullptr;
+  void* args[] = {const_cast<SteadyPlanes*>(&C.planes), &ST, &stats, &list, &count, &lflags, &gofs, &zc};
+  return hipExtLaunchKernel(one ? C.one : C.generic,
+                            grid_for(std::min<uint64_t>(ng, C.planes.G - g0)), dim3(256), args, 0, s, ev_start, ev_stop,
+                            0);
 }
 hipError_t launch_tick_list(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
                             int32_t* work_tick, uint32_t* work_count, uint32_t* list, uint32_t* count,

@@ -66,13 +66,62 @@ struct ListNext {
 hipError_t launch_tick_fused(int R, int sem, const DevPlanes& P, const Trace& T, int nticks, unsigned long long* stats,
                              uint32_t* list, uint32_t* count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
 // (g0, ng: the launch covers groups [g0, g0 + ng) only; g0 a multiple of 256;
-// zero_count: list counters the launch zeroes, block 0, before anything else;
-// steady: the kernel's steady form (tick_steady.hpp) — only for a tick of a
-// list-skipping call with every live group in the global ring phase, no
-// device counters and no timing diagnostics; lflags and zero_count unused)
+// zero_count: list counters the launch zeroes, block 0, before anything else)
 hipError_t launch_tick_lean(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* list,
                             uint32_t* count, int lflags, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
-                            uint64_t g0 = 0, uint64_t ng = ~0ull, uint32_t* zero_count = nullptr, bool steady = false);
+                            uint64_t g0 = 0, uint64_t ng = ~0ull, uint32_t* zero_count = nullptr);
+
+// The lean kernel's steady form (tick_steady.hpp) — only for the ticks of a
+// list-skipping call with every live group in the global ring phase, no
+// device counters and no timing diagnostics. Its launch arguments: what the
+// body reads of DevPlanes (constant between launches but for dbg_pass /
+// rec_nt, which the host sets between calls) ...
+struct SteadyPlanes {
+  const uint16_t* gmeta;
+  SsRec* gss;
+  uint16_t* grot;
+  int32_t* hb;
+  Strided<int32_t, 16> gshf;
+  int32_t* term;       // the entries' planes: the shared ring (SH, one row per slot: sh_cs = 0) or the replica rings
+  int64_t* value;
+  uint32_t* crc;
+  const uint32_t* crc_tab;
+  uint64_t gbase;
+  uint64_t cv_stride;  // staged client values: between a group's entries e and e+1 (0: the trace RNG)
+  uint32_t G, K, KP, kmask;
+  uint32_t dbg_pass, rec_nt;
+  uint32_t scap, shard_sb;
+};
+// ... and of Trace, with the tick's client entries, ring phase and staged
+// values' row worked out by the host.
+struct SteadyTick {
+  uint64_t seed;
+  int64_t tick;
+  const int64_t* cv;   // staged client values: entry 0 of group 0 at this tick (null: the trace RNG)
+  int32_t now;
+  uint32_t n;          // this tick's client entries
+  uint32_t ph;         // global ring phase of this tick's first entry
+};
+// What a call's steady launches share, worked out once per call
+// (steady_resolve): the planes' record, the instantiations for the engine's
+// (R, semantics, CRC, shared ring) — the generic one and, where the planes
+// admit it, the one-entry one (null otherwise; picked per launch by the
+// tick's entries) — and what a tick's record needs of DevPlanes.
+struct SteadyCall {
+  SteadyPlanes planes;
+  const void* generic;
+  const void* one;
+  const int64_t* cv;
+  int64_t cv_t0;
+  uint64_t cv_tstride;
+};
+hipError_t steady_resolve(int R, int sem, const DevPlanes& P, SteadyCall* out);
+// One launch over groups [g0, g0 + ng): fills the tick's record and the group
+// offset, nothing else. Returns the launch call's own status; *one_launches
+// (may be null) counts the launches of the one-entry instantiation.
+hipError_t launch_tick_steady(const SteadyCall& C, const Trace& T, unsigned long long* stats, uint32_t* list,
+                              uint32_t* count, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, uint64_t g0 = 0,
+                              uint64_t ng = ~0ull, uint64_t* one_launches = nullptr);
 
 hipError_t launch_tick_list(int R, int sem, const DevPlanes& P, const Trace& T, unsigned long long* stats, uint32_t* work,
                             int32_t* work_tick, uint32_t* work_count, uint32_t* list, uint32_t* count,

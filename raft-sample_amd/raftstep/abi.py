@@ -42,6 +42,7 @@ DIAG = {
     "list_return": 53, "list_return_trunc": 54, "list_stale": 55, "list_hwx": 56, "list_three_seg": 57,
     "list_isolated_replica": 58, "list_timer_fire": 59, "list_window_start": 60,
     "ticks": 64, "ticks_list_skipped": 65, "general_launches": 66, "ticks_steady_form": 67,
+    "launches_steady_one": 68, "ticks_split": 69,
 }
 
 

@@ -318,6 +318,56 @@ typedef struct raft_op_result {
 int raft_group_ops_batch(raft_engine* e, int64_t now_tick, const raft_group_op* ops, size_t n,
                          raft_op_result* out);
 
+/* ---- commit feed ----------------------------------------------------------
+ * The way out of the log: every entry a replica has committed, handed over
+ * once and in order, to apply or to acknowledge (main.go:330: "this is where
+ * the leader should answer the client once CommitIndex has advanced"; the
+ * CommitIndex updates at main.go:151-153 and 387-390). The device keeps one
+ * int32 cursor per (group, replica of the mask) from raft_feed_open to
+ * raft_feed_close / raft_engine_destroy; an engine without an open feed
+ * allocates nothing for it.
+ *
+ * A poll treats one pair with cursor c, CommitIndex cm, LastApplied l and
+ * high-water mark h (REF: h = l; ring depth K) like this:
+ *   hi = min(cm, l)           (a REF follower's CommitIndex may be l+1,
+ *                              main.go:152: that entry is delivered once it exists)
+ *   hi < c:  the pair is counted in `stalled` and left alone (a cursor never
+ *            moves backwards: a pair's stream is strictly increasing in index)
+ *   else     lo = min(max(c, h - K), hi); the lo - c entries that have left
+ *            the ring are counted in `lost` and skipped whatever `cap` is;
+ *            entries lo+1 .. hi are deliverable.
+ * The deliverable entries of all pairs, ordered by (group, replica, index),
+ * are cut at `cap`: the first `cap` are written to `out` and the cursors
+ * advance by exactly what was written (a pair may be cut in the middle).
+ * info->delivered is that number, info->pending the deliverable entries left.
+ * cap = 0 (out may then be NULL) only counts. The same state and cursors
+ * give the same bytes. Faulted groups are read like any other. */
+typedef struct raft_feed_entry {   /* 32 B */
+  uint64_t group;     /* global id: config.group_base + local group */
+  uint32_t replica;
+  int32_t  index;     /* 1-based log index */
+  int32_t  term;      /* Log.Term  (main.go:47) */
+  uint32_t crc;       /* the entry's CRC32C stamp; 0 when payload_crc is off */
+  int64_t  value;     /* Log.Value (main.go:48) */
+} raft_feed_entry;
+typedef struct raft_feed_info { uint64_t delivered, pending, lost, stalled; } raft_feed_info;
+/* Where the cursors start: at 0, at the current min(CommitIndex, LastApplied)
+ * (only what commits from now on), or at the caller's array ([G][R] int32,
+ * read for the replicas of the mask, none negative; what raft_feed_cursors
+ * returned resumes a feed exactly). */
+enum raft_feed_start { RAFT_FEED_FROM_START = 0, RAFT_FEED_FROM_COMMIT = 1, RAFT_FEED_FROM_CURSORS = 2 };
+/* replica_mask: bit r = replica r is fed (RAFT_EINVAL when 0 or with bits at
+ * or above R). Opening an open feed replaces it. */
+int raft_feed_open(raft_engine* e, uint32_t replica_mask, uint32_t start, const int32_t* cursors);
+/* RAFT_EINVAL without an open feed. Handler batches and raft_tick leave the
+ * feed open (and a poll leaves the steady tick's forms alone); whatever
+ * replaces the state (raft_init_*, raft_load_state, raft_checkpoint_load)
+ * closes it. No collective: each engine feeds its own shard. */
+int raft_feed_poll(raft_engine* e, raft_feed_entry* out, uint64_t cap, raft_feed_info* info);
+/* The cursors, [G][R] int32; -1 for replicas outside the mask. */
+int raft_feed_cursors(raft_engine* e, int32_t* out);
+int raft_feed_close(raft_engine* e);   /* (no open feed: nothing to do) */
+
 /* ---- multi-GPU statistics (RCCL over xGMI) -------------------------------
  * Groups shard by id (config.group_base); the only collective is the sum of
  * tick statistics. raft_tick reduces per-tick records on the device (NSTAT

@@ -297,6 +297,23 @@ struct raft_engine {
   std::vector<hipEvent_t> comm_ev;
   std::vector<hipEvent_t> comm_pre;   // markers before each all-reduce since the last completed wait (wait_stream)
   size_t comm_pre_used = 0;
+  // Commit feed (raft_feed_*; k_feed.hip). Open: feed_mask != 0. The cursors
+  // ([G][feed_nm] int32), the count pass's block sums and their scan and the
+  // poll's totals live from open to close; the records' staging buffer is kept
+  // across polls and grows by doubling; feed_tot is the totals' pinned copy.
+  uint32_t feed_mask = 0, feed_nm = 0, feed_nb = 0;
+  int32_t* feed_cur = nullptr;
+  uint32_t* feed_bsum = nullptr;
+  uint64_t* feed_boff = nullptr;
+  unsigned long long* feed_dtot = nullptr;   // the count pass's accumulators: -, lost, stalled, -
+  unsigned long long* feed_tot = nullptr;    // pinned, coherent: the poll's total, lost, stalled (feed_scan_kernel)
+  int feed_paired = 1;          // RAFTSTEP_FEED_PAIRED=0: every lane stores its own record (A/B; same bytes)
+  void* feed_stage = nullptr;
+  uint64_t feed_stage_cap = 0;  // records
+  uint64_t feed_bytes = 0;      // of the cursors (raft_engine_info while the feed is open)
+  // RAFTSTEP_FEED_TIME=1 (read by raft_feed_open): one stderr line per poll with the spans between HIP events
+  // around its launches (count + scan + totals, emit, the copy out); costs a synchronise per poll
+  hipEvent_t feed_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int nranks = 1, rank = 0;
   uint64_t allreduces = 0;      // ncclAllReduce calls issued (diagnostics)
   bool comm_side = false;       // a sum on comm_stream the engine stream has not waited for
@@ -414,10 +431,37 @@ void host_mutation(raft_engine* e) {
   e->run_valid = false;   // entries from here on are not the trace's
   e->steady_origin = e->steady_ok = e->phase_ok = false;   // (the list skip needs a fresh proof)
 }
+// Commit feed: frees what raft_feed_open allocated (no poll is in flight: each
+// one ends with a synchronise). The staging buffer goes too.
+void feed_release(raft_engine* e) {
+  if (!e->feed_mask && !e->feed_stage) return;
+  (void)hipSetDevice(e->cfg.device);
+  if (e->feed_cur) (void)hipFree(e->feed_cur);
+  if (e->feed_bsum) (void)hipFree(e->feed_bsum);
+  if (e->feed_boff) (void)hipFree(e->feed_boff);
+  if (e->feed_dtot) (void)hipFree(e->feed_dtot);
+  if (e->feed_tot) (void)hipHostFree(e->feed_tot);
+  if (e->feed_stage) (void)hipFree(e->feed_stage);
+  for (hipEvent_t& x : e->feed_ev) {
+    if (x) (void)hipEventDestroy(x);
+    x = nullptr;
+  }
+  e->feed_cur = nullptr;
+  e->feed_bsum = nullptr;
+  e->feed_boff = nullptr;
+  e->feed_dtot = e->feed_tot = nullptr;
+  e->feed_stage = nullptr;
+  e->feed_stage_cap = 0;
+  e->feed_mask = e->feed_nm = e->feed_nb = 0;
+  e->device_bytes -= e->feed_bytes;
+  e->feed_bytes = 0;
+}
+
 // A call that replaces the state starts by dropping the list-skip proof (the
 // conservative direction, whatever happens next) ...
 void state_replacing(raft_engine* e) {
   host_mutation(e);
+  feed_release(e);      // (the cursors describe the old logs)
   e->vx_live = false;   // (the state is being replaced: no suffix survives)
   e->sh_live = false;   // (nor a shared entry: every rotation is rewritten)
 }
@@ -856,6 +900,7 @@ int raft_engine_destroy(raft_engine* e) {
   if (e->gen_stream) (void)hipStreamDestroy(e->gen_stream);
   if (e->list_stream) (void)hipStreamDestroy(e->list_stream);
   if (e->half_stream) (void)hipStreamDestroy(e->half_stream);
+  feed_release(e);
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->hist) (void)hipFree(e->hist);
   if (e->tstat) (void)hipFree(e->tstat);
@@ -2406,6 +2451,145 @@ int raft_nodelog(raft_engine* e, uint64_t group, char* buf, size_t cap) {
   if (out.size() + 1 > cap) return fail(RAFT_ERANGE, "nodelog needs %zu bytes", out.size() + 1);
   std::memcpy(buf, out.c_str(), out.size() + 1);
   return int(out.size());
+}
+
+// ---- commit feed -----------------------------------------------------------
+// Reads the state as raft_state_digest does (settle_check, vx_flush, shared
+// entries from the shared ring itself): nothing here takes a group out of its
+// shared form or ends the steady tick's forms.
+
+int raft_feed_open(raft_engine* e, uint32_t replica_mask, uint32_t start, const int32_t* cursors) {
+  if (!e) return fail(RAFT_EINVAL, "null engine");
+  const uint64_t G = e->cfg.groups, R = e->cfg.replicas;
+  if (!replica_mask || (replica_mask >> R))
+    return fail(RAFT_EINVAL, "replica_mask %#x: needs at least one of the %llu replicas and no other bit", replica_mask,
+                (unsigned long long)R);
+  if (start > RAFT_FEED_FROM_CURSORS) return fail(RAFT_EINVAL, "start %u is no raft_feed_start", start);
+  if (start == RAFT_FEED_FROM_CURSORS && !cursors) return fail(RAFT_EINVAL, "RAFT_FEED_FROM_CURSORS needs cursors");
+  const uint32_t nm = uint32_t(__builtin_popcount(replica_mask));
+  std::vector<int32_t> h;
+  if (start == RAFT_FEED_FROM_CURSORS) {
+    h.resize(G * nm);
+    for (uint64_t g = 0; g < G; ++g)
+      for (uint64_t r = 0, k = 0; r < R; ++r) {
+        if (!((replica_mask >> r) & 1u)) continue;
+        const int32_t c = cursors[g * R + r];
+        if (c < 0) return fail(RAFT_EINVAL, "cursor of group %llu replica %llu is negative", (unsigned long long)g,
+                               (unsigned long long)r);
+        h[g * nm + k++] = c;
+      }
+  }
+  if (int rc = settle_check(e)) return rc;
+  if (start == RAFT_FEED_FROM_COMMIT)
+    if (int rc = vx_flush(e)) return rc;
+  feed_release(e);
+  HIPCHK(hipSetDevice(e->cfg.device));
+  const uint32_t nb = uint32_t((G + 255) / 256);
+  const size_t cb = size_t(G) * nm * 4;
+  hipError_t rc = hipMalloc(reinterpret_cast<void**>(&e->feed_cur), cb);
+  if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&e->feed_bsum), size_t(nb) * 4);
+  if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&e->feed_boff), size_t(nb) * 8);
+  if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&e->feed_dtot), 32);
+  if (rc == hipSuccess) rc = hipHostMalloc(reinterpret_cast<void**>(&e->feed_tot), 32, hipHostMallocCoherent);
+  if (rc == hipSuccess) rc = hipMemsetAsync(e->feed_dtot, 0, 32, e->stream);
+  const char* fp = getenv("RAFTSTEP_FEED_PAIRED");
+  e->feed_paired = fp ? atoi(fp) != 0 : 1;
+  const char* ft = getenv("RAFTSTEP_FEED_TIME");
+  if (ft && atoi(ft) > 0)
+    for (hipEvent_t& x : e->feed_ev)
+      if (rc == hipSuccess) rc = hipEventCreate(&x);
+  e->feed_mask = replica_mask;   // (open from here on: feed_release frees whatever was allocated)
+  e->feed_nm = nm;
+  e->feed_nb = nb;
+  if (rc == hipSuccess) {
+    e->feed_bytes = cb;
+    e->device_bytes += cb;
+    if (start == RAFT_FEED_FROM_START) rc = hipMemsetAsync(e->feed_cur, 0, cb, e->stream);
+    else if (start == RAFT_FEED_FROM_CURSORS)
+      rc = hipMemcpyAsync(e->feed_cur, h.data(), cb, hipMemcpyHostToDevice, e->stream);
+    else
+      rc = launch_feed_count(e->R, e->P, e->cfg.semantics == RAFT_SEM_RAFT, replica_mask, nm, e->feed_cur, e->feed_bsum,
+                             e->feed_dtot, 1, e->stream);
+  }
+  if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);
+  if (rc != hipSuccess) {
+    feed_release(e);
+    return fail(rc == hipErrorOutOfMemory ? RAFT_ENOMEM : RAFT_EHIP, "raft_feed_open: %s", hipGetErrorString(rc));
+  }
+  return RAFT_OK;
+}
+
+int raft_feed_poll(raft_engine* e, raft_feed_entry* out, uint64_t cap, raft_feed_info* info) {
+  if (!e || !info) return fail(RAFT_EINVAL, "null argument");
+  if (cap && !out) return fail(RAFT_EINVAL, "raft_feed_poll: cap %llu without a buffer", (unsigned long long)cap);
+  if (!e->feed_mask) return fail(RAFT_EINVAL, "raft_feed_poll: no feed is open (raft_feed_open)");
+  if (int rc = settle_check(e)) return rc;
+  if (int rc = vx_flush(e)) return rc;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  const int raft = e->cfg.semantics == RAFT_SEM_RAFT;
+  const bool timed = e->feed_ev[4] != nullptr;
+  if (timed) HIPCHK(hipEventRecord(e->feed_ev[0], e->stream));
+  HIPCHK(launch_feed_count(e->R, e->P, raft, e->feed_mask, e->feed_nm, e->feed_cur, e->feed_bsum, e->feed_dtot, 0,
+                           e->stream));
+  HIPCHK(launch_feed_scan(e->feed_bsum, e->feed_boff, e->feed_nb, e->feed_dtot, e->feed_tot, e->stream));
+  if (timed) HIPCHK(hipEventRecord(e->feed_ev[1], e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));   // the totals size the emit pass and the copy
+  const uint64_t total = e->feed_tot[0];
+  const uint64_t n = std::min<uint64_t>(cap, total);
+  if (n) {
+    if (n > e->feed_stage_cap) {   // (idle: the stream was synchronised above)
+      const uint64_t want = std::max<uint64_t>({n, e->feed_stage_cap * 2, uint64_t(1) << 15});
+      if (e->feed_stage) HIPCHK(hipFree(e->feed_stage));
+      e->feed_stage = nullptr;
+      e->feed_stage_cap = 0;
+      hipError_t rc = hipMalloc(&e->feed_stage, want * sizeof(raft_feed_entry));
+      if (rc != hipSuccess)
+        return fail(RAFT_ENOMEM, "raft_feed_poll: %llu records of staging: %s", (unsigned long long)want,
+                    hipGetErrorString(rc));
+      e->feed_stage_cap = want;
+    }
+    if (timed) HIPCHK(hipEventRecord(e->feed_ev[4], e->stream));
+    HIPCHK(launch_feed_emit(e->R, e->P, raft, e->feed_mask, e->feed_nm, e->feed_cur, e->feed_boff, n, e->feed_stage,
+                            e->feed_paired, e->stream));
+    if (timed) HIPCHK(hipEventRecord(e->feed_ev[2], e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->feed_stage, n * sizeof(raft_feed_entry), hipMemcpyDeviceToHost, e->stream));
+    if (timed) HIPCHK(hipEventRecord(e->feed_ev[3], e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  if (timed) {
+    float a = 0, b = 0, c = 0;
+    HIPCHK(hipEventElapsedTime(&a, e->feed_ev[0], e->feed_ev[1]));
+    if (n) {
+      HIPCHK(hipEventElapsedTime(&b, e->feed_ev[4], e->feed_ev[2]));   // (the emit kernel alone)
+      HIPCHK(hipEventElapsedTime(&c, e->feed_ev[2], e->feed_ev[3]));
+    }
+    fprintf(stderr, "raft_feed_poll: delivered %llu count_scan_us %.1f emit_us %.1f copy_us %.1f\n",
+            (unsigned long long)n, a * 1e3, b * 1e3, c * 1e3);
+  }
+  info->delivered = n;
+  info->pending = total - n;
+  info->lost = e->feed_tot[1];
+  info->stalled = e->feed_tot[2];
+  return RAFT_OK;
+}
+
+int raft_feed_cursors(raft_engine* e, int32_t* out) {
+  if (!e || !out) return fail(RAFT_EINVAL, "null argument");
+  if (!e->feed_mask) return fail(RAFT_EINVAL, "raft_feed_cursors: no feed is open (raft_feed_open)");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  const uint64_t G = e->cfg.groups, R = e->cfg.replicas, nm = e->feed_nm;
+  std::vector<int32_t> h(G * nm);
+  HIPCHK(hipMemcpyAsync(h.data(), e->feed_cur, h.size() * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  for (uint64_t g = 0; g < G; ++g)
+    for (uint64_t r = 0, k = 0; r < R; ++r) out[g * R + r] = ((e->feed_mask >> r) & 1u) ? h[g * nm + k++] : -1;
+  return RAFT_OK;
+}
+
+int raft_feed_close(raft_engine* e) {
+  if (!e) return fail(RAFT_EINVAL, "null engine");
+  feed_release(e);
+  return RAFT_OK;
 }
 
 }  // extern "C"

@@ -186,6 +186,23 @@ hipError_t launch_vx_flush(int R, const DevPlanes& P, uint64_t Qb, uint32_t E, u
                            hipStream_t s);
 // SH (raft_device.hpp ROT_SH): every group's shared entries into its replica rings
 hipError_t launch_sh_flush(int R, const DevPlanes& P, hipStream_t s);
+// Commit feed (k_feed.hip; raft_feed_*). cursors: [G][nm] int32, one per
+// group and replica of `mask` (nm = its bits, in replica order).
+// launch_feed_count: per block the entries it has to deliver (bsum), the
+// poll's lost entries and stalled pairs (added to tot[1], tot[2], zero between
+// polls), cursors moved past lost entries; mode 1 instead sets every cursor
+// to min(CommitIndex, LastApplied) and counts nothing.
+// launch_feed_scan: boff = exclusive scan of bsum[nb]; res (pinned host
+// memory) = {the total, lost, stalled}; tot[1], tot[2] zeroed again.
+// launch_feed_emit: records [0, cap) of the (group, replica, index) order to
+// `out` (32 B each, raft_feed_entry), cursors advanced by what was written;
+// paired: the store form (k_feed.hip).
+hipError_t launch_feed_count(int R, const DevPlanes& P, int raft, uint32_t mask, uint32_t nm, int32_t* cursors,
+                             uint32_t* bsum, unsigned long long* tot, int mode, hipStream_t s);
+hipError_t launch_feed_scan(const uint32_t* bsum, uint64_t* boff, uint32_t nb, unsigned long long* tot,
+                            unsigned long long* res, hipStream_t s);
+hipError_t launch_feed_emit(int R, const DevPlanes& P, int raft, uint32_t mask, uint32_t nm, int32_t* cursors,
+                            const uint64_t* boff, uint64_t cap, void* out, int paired, hipStream_t s);
 hipError_t launch_stream_probe(int R, const uint16_t* a, SsRec* b, const uint16_t* c, int32_t* d, int32_t* rt,
                                int64_t* rv, uint32_t n, uint32_t slot, uint32_t kslots, hipStream_t s,
                                uint32_t mode = 0);

@@ -68,6 +68,20 @@ class Engine {
     return s;
   }
 
+  // Commit feed (main.go:330; CommitIndex updates at 151-153 and 387-390): every fed replica's newly
+  // committed entries, once and in (group, replica, index) order. Poll fills `out` with at most `cap` records.
+  void FeedOpen(uint32_t replica_mask, uint32_t start = RAFT_FEED_FROM_COMMIT) {
+    check(raft_feed_open(h_, replica_mask, start, nullptr), "raft_feed_open");
+  }
+  raft_feed_info FeedPoll(std::vector<raft_feed_entry>& out, uint64_t cap) {
+    out.resize(cap);
+    raft_feed_info info{};
+    check(raft_feed_poll(h_, out.data(), cap, &info), "raft_feed_poll");
+    out.resize(info.delivered);
+    return info;
+  }
+  void FeedClose() { check(raft_feed_close(h_), "raft_feed_close"); }
+
   // Snapshot of every group's state (canonical group-major arrays).
   struct Snapshot {
     uint32_t R = 0, K = 0;

@@ -181,11 +181,22 @@ VOTE_REQ = np.dtype([("group", "<u8"), ("to", "<u4"), ("candidate_id", "<u4"), (
 VOTE_RESP = np.dtype([("term", "<i8"), ("vote_granted", "<i4"), ("fault", "<i4")], align=True)
 GROUP_OP = np.dtype([("group", "<u8"), ("replica", "<u4"), ("kind", "<u4"), ("arg", "<i8")], align=True)
 OP_RESULT = np.dtype([("status", "<i4"), ("fault", "<i4"), ("value", "<i8")], align=True)
+# commit feed (raft_feed_entry / raft_feed_info)
+FEED_ENTRY = np.dtype([("group", "<u8"), ("replica", "<u4"), ("index", "<i4"), ("term", "<i4"), ("crc", "<u4"),
+                       ("value", "<i8")], align=True)
+FEED_FROM_START, FEED_FROM_COMMIT, FEED_FROM_CURSORS = 0, 1, 2   # enum raft_feed_start
+FEED_START = {"start": FEED_FROM_START, "commit": FEED_FROM_COMMIT, "cursors": FEED_FROM_CURSORS}
+
+
+class FeedInfo(C.Structure):
+    _fields_ = [("delivered", C.c_uint64), ("pending", C.c_uint64), ("lost", C.c_uint64), ("stalled", C.c_uint64)]
+
 
 assert AE_REQ.itemsize == 64 and AE_RESP.itemsize == 24 and LOG_ENTRY.itemsize == 16
 assert VOTE_REQ.itemsize == 40 and VOTE_RESP.itemsize == 16
 assert GROUP_OP.itemsize == 24 and OP_RESULT.itemsize == 16
 assert C.sizeof(Config) == 120, C.sizeof(Config)
+assert FEED_ENTRY.itemsize == 32 and C.sizeof(FeedInfo) == 32
 
 # exported symbols of libraftstep.so (the C-ABI), with ctypes signatures
 P = C.c_void_p
@@ -225,12 +236,18 @@ SIGNATURES = {
     "raft_stream_probe": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "raft_debug_group_words": (C.c_int, [P, C.c_uint64, P, C.c_uint32]),
+    "raft_feed_open": (C.c_int, [P, C.c_uint32, C.c_uint32, P]),
+    "raft_feed_poll": (C.c_int, [P, P, C.c_uint64, P]),
+    "raft_feed_cursors": (C.c_int, [P, P]),
+    "raft_feed_close": (C.c_int, [P]),
 }
 
 
 # measurement / diagnostics entry points added in round 5: an older build
 # loaded through RAFTSTEP_LIB (A/B runs) may lack them
-OPTIONAL = ("raft_debug_diag_mode", "raft_stream_probe", "raft_engine_features")
+# (and the commit feed, added later still)
+OPTIONAL = ("raft_debug_diag_mode", "raft_stream_probe", "raft_engine_features",
+            "raft_feed_open", "raft_feed_poll", "raft_feed_cursors", "raft_feed_close")
 FEATURE_SHARED_ENTRIES, FEATURE_VIRTUAL_SUFFIXES = 1, 2   # raft_engine_features (include/raftstep.h)
 PROBE_PLAIN_RING, PROBE_NT_RECORD, PROBE_NO_HEARTBEAT = 1, 2, 4   # raft_stream_probe flags
 

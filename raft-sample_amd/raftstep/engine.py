@@ -160,6 +160,60 @@ class Engine:
     def load_checkpoint(self, path):
         _check(self.lib.raft_checkpoint_load(self.h, os.fsencode(path)))
 
+    # -- commit feed ---------------------------------------------------
+    def feed_open(self, replicas=None, start="commit", cursors=None):
+        """Open the commit feed (raft_feed_open). replicas: an iterable of
+        replica ids or a bit mask, None = all. start: "start" (cursors 0),
+        "commit" (only what commits from now on) or "cursors" (the [G][R]
+        int32 array given, e.g. what feed_cursors() returned)."""
+        R = self.cfg.replicas
+        if replicas is None:
+            mask = (1 << R) - 1
+        elif isinstance(replicas, (int, np.integer)):
+            mask = int(replicas)
+        else:
+            mask = 0
+            for r in replicas:
+                if int(r) < 0:
+                    raise ValueError(f"replica {r}")
+                mask |= 1 << int(r)
+        if not 0 <= mask < 1 << 32:
+            raise ValueError(f"replica mask {mask:#x}")
+        cur = None
+        if cursors is not None:
+            cur = np.ascontiguousarray(cursors, dtype=np.int32)
+            if cur.shape != (self.cfg.groups, R):
+                raise ValueError(f"feed cursors: shape {cur.shape}, expected ({self.cfg.groups}, {R})")
+        st = abi.FEED_START[start] if isinstance(start, str) else int(start)
+        _check(self.lib.raft_feed_open(self.h, mask, st, _ptr(cur)))
+
+    def feed_poll(self, cap=None):
+        """Drain newly committed entries (raft_feed_poll): (FEED_ENTRY array
+        ordered by (group, replica, index), info dict with delivered, pending,
+        lost, stalled). cap=None counts first, then takes everything."""
+        info = abi.FeedInfo()
+        first = None
+        if cap is None:
+            _check(self.lib.raft_feed_poll(self.h, None, 0, C.byref(info)))
+            first = info.lost, info.stalled   # (the counting poll already skipped the lost entries)
+            cap = info.pending
+        out = np.zeros(int(cap), abi.FEED_ENTRY)
+        _check(self.lib.raft_feed_poll(self.h, _ptr(out), int(cap), C.byref(info)))
+        d = {k: int(getattr(info, k)) for k, _ in abi.FeedInfo._fields_}
+        if first is not None:
+            d["lost"] += int(first[0])
+            d["stalled"] = int(first[1])
+        return out[:d["delivered"]], d
+
+    def feed_cursors(self):
+        """The feed's cursors, int32 [G][R]; -1 for replicas outside the mask."""
+        out = np.zeros((self.cfg.groups, self.cfg.replicas), np.int32)
+        _check(self.lib.raft_feed_cursors(self.h, _ptr(out)))
+        return out
+
+    def feed_close(self):
+        _check(self.lib.raft_feed_close(self.h))
+
     # -- the fused tick ------------------------------------------------
     def tick(self, first_tick, nticks=1, stats=True):
         if stats:

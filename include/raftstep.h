@@ -368,6 +368,57 @@ int raft_feed_poll(raft_engine* e, raft_feed_entry* out, uint64_t cap, raft_feed
 int raft_feed_cursors(raft_engine* e, int32_t* out);
 int raft_feed_close(raft_engine* e);   /* (no open feed: nothing to do) */
 
+/* ---- group directory ------------------------------------------------------
+ * The way out of the fault codes, and the way back in: find groups by what is
+ * wrong with them, read the canonical view of a list of groups, and restart
+ * single groups (what an operator of the Go program does to a process that
+ * panicked). The scan and the store read the state on the device as
+ * raft_state_digest does: they take no group out of its shared form, keep the
+ * steady tick's forms and leave an open feed alone.
+ *
+ * raft_group_scan: a group g in [first_group, G) (local ids) is a hit when
+ *   select & RAFT_SELECT_FAULTED    and its fault code is not 0, or
+ *   select & RAFT_SELECT_LEADERLESS and its fault code is 0 and no replica's
+ *                                   State is Leader (a live group waiting for
+ *                                   an election; a frozen group is never
+ *                                   reported as leaderless).
+ * Hits come in ascending group order; the first `cap` are written to `out`
+ * (cap = 0 only counts, out may then be NULL). info->matched = every hit in
+ * the range, info->written = min(cap, matched), info->next_group = the local
+ * id after the last hit written, G when nothing is left (written == matched),
+ * first_group when nothing was written and hits are left (cap = 0): a caller
+ * pages with first_group = next_group. The same state gives the same bytes.
+ * RAFT_EINVAL: select 0 or with unknown bits, cap > 0 without out;
+ * RAFT_ERANGE: first_group > G (first_group == G is an empty scan). */
+enum raft_group_select { RAFT_SELECT_FAULTED = 1u, RAFT_SELECT_LEADERLESS = 2u };
+typedef struct raft_group_hit {   /* 16 B */
+  uint64_t group;     /* global id: config.group_base + local */
+  uint32_t local;     /* what every batch call and the two calls below take */
+  uint8_t  fault;     /* enum raft_fault */
+  uint8_t  leader;    /* lowest-id replica whose State is Leader, 0xFF: none */
+  uint16_t reserved;  /* 0 */
+} raft_group_hit;
+typedef struct raft_scan_info { uint64_t matched, written, next_group; } raft_scan_info;
+int raft_group_scan(raft_engine* e, uint32_t select, uint64_t first_group, raft_group_hit* out, uint64_t cap,
+                    raft_scan_info* info);
+/* The canonical view of groups[0..n) (local ids, in any order, repeats
+ * allowed), indexed by the list position i with the per-group shapes of
+ * raft_store_state_range and byte-identical to the rows raft_store_state
+ * returns for those groups; NULL fields are skipped. n = 0 is a no-op; an id
+ * >= G is RAFT_ERANGE with nothing written. */
+int raft_store_groups(raft_engine* e, const uint64_t* groups, uint64_t n, raft_state_view* v);
+/* NewNode (main.go:59-76) for every replica of each listed group followed by
+ * the FollowerRun entry at virtual tick `tick0` (main.go:113-115): exactly what
+ * raft_init_new_nodes(tick0) writes for that group (the Go node keeps nothing
+ * on disk: term 0, no vote, empty logs, timers drawn from the trace RNG by the
+ * global id and tick0, fault and isolation record 0). Every other group is
+ * untouched, bit for bit. Ids must be distinct (RAFT_EINVAL) and < G
+ * (RAFT_ERANGE); any error leaves the state as it was, n = 0 changes nothing.
+ * Like a handler batch, a restart ends the steady tick's list skip and steady
+ * form until the next raft_init_steady. An open feed stays open: every fed
+ * cursor of a restarted group becomes 0, the others do not move. */
+int raft_restart_groups(raft_engine* e, const uint64_t* groups, uint64_t n, int64_t tick0);
+
 /* ---- multi-GPU statistics (RCCL over xGMI) -------------------------------
  * Groups shard by id (config.group_base); the only collective is the sum of
  * tick statistics. raft_tick reduces per-tick records on the device (NSTAT

@@ -2592,6 +2592,210 @@ int raft_feed_close(raft_engine* e) {
   return RAFT_OK;
 }
 
+// ---- group directory -------------------------------------------------------
+// The scan and the store read the state as raft_state_digest does
+// (settle_check, vx_flush, sh_heartbeat while shared entries are live; shared
+// entries from the shared ring itself). Everything is staged in the handler
+// batches' buffer (raft_engine::stage).
+
+static int directory_read_begin(raft_engine* e) {
+  if (int rc = settle_check(e)) return rc;
+  if (int rc = vx_flush(e)) return rc;
+  if (e->sh_live)
+    if (int rc = sh_heartbeat(e)) return rc;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  return RAFT_OK;
+}
+
+int raft_group_scan(raft_engine* e, uint32_t select, uint64_t first_group, raft_group_hit* out, uint64_t cap,
+                    raft_scan_info* info) {
+  static_assert(sizeof(raft_group_hit) == 16, "raft_group_hit is 16 B");
+  if (!e || !info) return fail(RAFT_EINVAL, "null argument");
+  if (!select || (select & ~uint32_t(RAFT_SELECT_FAULTED | RAFT_SELECT_LEADERLESS)))
+    return fail(RAFT_EINVAL, "raft_group_scan: select %#x is no set of raft_group_select bits", select);
+  if (cap && !out) return fail(RAFT_EINVAL, "raft_group_scan: cap %llu without a buffer", (unsigned long long)cap);
+  const uint64_t G = e->cfg.groups;
+  if (first_group > G)
+    return fail(RAFT_ERANGE, "raft_group_scan: first_group %llu past the engine's %llu groups",
+                (unsigned long long)first_group, (unsigned long long)G);
+  if (int rc = directory_read_begin(e)) return rc;
+  info->matched = info->written = 0;
+  info->next_group = G;
+  if (first_group == G) return RAFT_OK;
+  const uint32_t first = uint32_t(first_group);
+  const uint32_t nb = uint32_t((G + 255) / 256) - (first >> 8);
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t b_sum = al(size_t(nb) * 4), b_off = al(size_t(nb) * 8), b_tot = 256;
+  const size_t fixed = b_sum + b_off + b_tot;
+  unsigned long long res[4] = {0, 0, 0, 0};
+  // The hits' room is known only after the count; if the buffer then has to
+  // grow (ensure_stage frees the old one), count and scan run again in the new one.
+  uint64_t room = std::min<uint64_t>(cap, 1u << 16);
+  // RAFTSTEP_GROUPS_TIME=1: one stderr line per scan with the spans between HIP events around its three
+  // launches (tools/groups_probe.py; the events cost their creation and a synchronise per call)
+  const char* gt = getenv("RAFTSTEP_GROUPS_TIME");
+  hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  struct EvGuard {
+    hipEvent_t* v;
+    ~EvGuard() {
+      for (int i = 0; i < 5; ++i)
+        if (v[i]) (void)hipEventDestroy(v[i]);
+    }
+  } ev_guard{tev};
+  if (gt && atoi(gt) > 0)
+    for (hipEvent_t& x : tev) HIPCHK(hipEventCreate(&x));
+  for (int pass = 0; pass < 2; ++pass) {
+    if (int rc = ensure_stage(e, fixed + size_t(room) * sizeof(raft_group_hit))) return rc;
+    char* base = static_cast<char*>(e->stage);
+    uint32_t* bsum = reinterpret_cast<uint32_t*>(base);
+    uint64_t* boff = reinterpret_cast<uint64_t*>(base + b_sum);
+    // eight words: [0, 4) feed_scan_kernel's accumulators (unused here, zero), [4, 7) its results, [7] next_group
+    unsigned long long* tot = reinterpret_cast<unsigned long long*>(base + b_sum + b_off);
+    HIPCHK(hipMemsetAsync(tot, 0, 64, e->stream));
+    if (tev[0]) HIPCHK(hipEventRecord(tev[0], e->stream));
+    HIPCHK(launch_group_count(e->R, e->P, select, first, bsum, e->stream));
+    if (tev[0]) HIPCHK(hipEventRecord(tev[1], e->stream));
+    HIPCHK(launch_feed_scan(bsum, boff, nb, tot, tot + 4, e->stream));
+    if (tev[0]) HIPCHK(hipEventRecord(tev[2], e->stream));
+    HIPCHK(hipMemcpyAsync(res, tot + 4, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));   // the total sizes the emit pass and the copy
+    const uint64_t n = std::min<uint64_t>(cap, res[0]);
+    if (n <= room) break;
+    room = n;
+  }
+  const uint64_t matched = res[0], n = std::min<uint64_t>(cap, matched);
+  uint64_t next = n == matched ? G : first_group;
+  if (n) {
+    char* base = static_cast<char*>(e->stage);
+    uint64_t* boff = reinterpret_cast<uint64_t*>(base + b_sum);
+    unsigned long long* d_next = reinterpret_cast<unsigned long long*>(base + b_sum + b_off) + 7;
+    void* hits = base + fixed;
+    unsigned long long h_next = 0;
+    if (tev[0]) HIPCHK(hipEventRecord(tev[3], e->stream));
+    HIPCHK(launch_group_emit(e->R, e->P, select, first, boff, n, hits, d_next, e->stream));
+    if (tev[0]) HIPCHK(hipEventRecord(tev[4], e->stream));
+    HIPCHK(hipMemcpyAsync(out, hits, size_t(n) * sizeof(raft_group_hit), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&h_next, d_next, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (n < matched) next = h_next;
+  }
+  if (tev[0]) {
+    float c = 0, sc = 0, em = 0;
+    HIPCHK(hipEventElapsedTime(&c, tev[0], tev[1]));
+    HIPCHK(hipEventElapsedTime(&sc, tev[1], tev[2]));
+    if (n) HIPCHK(hipEventElapsedTime(&em, tev[3], tev[4]));
+    fprintf(stderr, "raft_group_scan: matched %llu written %llu count_us %.1f scan_us %.1f emit_us %.1f\n",
+            (unsigned long long)matched, (unsigned long long)n, c * 1e3, sc * 1e3, em * 1e3);
+  }
+  info->matched = matched;
+  info->written = n;
+  info->next_group = next;
+  return RAFT_OK;
+}
+
+int raft_store_groups(raft_engine* e, const uint64_t* groups, uint64_t n, raft_state_view* v) {
+  if (!e || !v || (n && !groups)) return fail(RAFT_EINVAL, "null argument");
+  const uint64_t G = e->cfg.groups, R = e->cfg.replicas, K = e->cfg.ring_depth;
+  std::vector<uint32_t> ids(n);
+  for (uint64_t i = 0; i < n; ++i) {
+    if (groups[i] >= G)
+      return fail(RAFT_ERANGE, "raft_store_groups: element %llu: group %llu outside the engine's %llu",
+                  (unsigned long long)i, (unsigned long long)groups[i], (unsigned long long)G);
+    ids[i] = uint32_t(groups[i]);
+  }
+  if (int rc = directory_read_begin(e)) return rc;
+  if (!n) return RAFT_OK;
+  // (without payload_crc the stamps read back as 0: zeroed here, nothing gathered or copied for them)
+  uint32_t* const crc_rows = e->cfg.payload_crc ? v->log_crc : nullptr;
+  if (v->log_crc && !crc_rows) std::memset(v->log_crc, 0, size_t(n) * R * K * 4);
+  // the view's fields: host pointer, the staging pointer's slot in GatherOut, bytes per group
+  GatherOut o{};
+  struct Field { void* host; void** dev; size_t per; };
+  const Field fields[] = {
+      {v->role, reinterpret_cast<void**>(&o.role), R},
+      {v->voted, reinterpret_cast<void**>(&o.voted), R},
+      {v->term, reinterpret_cast<void**>(&o.term), R * 4},
+      {v->last, reinterpret_cast<void**>(&o.last), R * 4},
+      {v->commit, reinterpret_cast<void**>(&o.commit), R * 4},
+      {v->deadline, reinterpret_cast<void**>(&o.deadline), R * 4},
+      {v->timeout, reinterpret_cast<void**>(&o.timeout), R * 4},
+      {v->match, reinterpret_cast<void**>(&o.match), R * R * 4},
+      {v->fault, reinterpret_cast<void**>(&o.fault), 1},
+      {v->log_term, reinterpret_cast<void**>(&o.log_term), R * K * 4},
+      {v->log_value, reinterpret_cast<void**>(&o.log_value), R * K * 8},
+      {crc_rows, reinterpret_cast<void**>(&o.log_crc), R * K * 4},
+      {v->next, reinterpret_cast<void**>(&o.next), R * R * 4},
+      {v->hwm, reinterpret_cast<void**>(&o.hwm), R * 4},
+      {v->iso_victim, reinterpret_cast<void**>(&o.iso_victim), 1},
+  };
+  size_t per = 0;
+  for (const Field& f : fields)
+    if (f.host) per += f.per;
+  if (!per) return RAFT_OK;
+  // chunks of groups bound the staging: the ids, then each field's rows of one chunk
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const uint64_t chunk = std::min<uint64_t>(n, std::max<uint64_t>(256, (uint64_t(32) << 20) / per));
+  const size_t b_ids = al(size_t(n) * 4);
+  size_t need = b_ids;
+  for (const Field& f : fields)
+    if (f.host) need += al(f.per * chunk);
+  if (int rc = ensure_stage(e, need)) return rc;
+  char* base = static_cast<char*>(e->stage);
+  uint32_t* d_ids = reinterpret_cast<uint32_t*>(base);
+  size_t off = b_ids;
+  for (const Field& f : fields) {
+    if (!f.host) continue;
+    *f.dev = base + off;
+    off += al(f.per * chunk);
+  }
+  HIPCHK(hipMemcpyAsync(d_ids, ids.data(), size_t(n) * 4, hipMemcpyHostToDevice, e->stream));
+  const int raft = e->cfg.semantics == RAFT_SEM_RAFT;
+  for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
+    const uint64_t nc = std::min<uint64_t>(chunk, n - c0);
+    // (the stream orders this chunk's kernels after the last chunk's copies out of the same buffers)
+    HIPCHK(launch_gather(e->R, e->P, raft, d_ids + c0, uint32_t(nc), o, e->stream));
+    for (const Field& f : fields)
+      if (f.host)
+        HIPCHK(hipMemcpyAsync(static_cast<char*>(f.host) + c0 * f.per, *f.dev, nc * f.per, hipMemcpyDeviceToHost,
+                              e->stream));
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return RAFT_OK;
+}
+
+// Host-side state: the handler batches' route (settle_check, ring_flush,
+// host_mutation). ring_flush first, so that no listed group holds shared
+// entries or a virtual suffix whose marks (ROT_SH in grot, M_VX in gmeta) the
+// new words would clear while GSeg::shf and the shared ring still describe the
+// old log; host_mutation because the restarted groups leave the compressed
+// steady state the list skip and the steady form are proven for, and their
+// entries are no longer the trace's run (group directory).
+int raft_restart_groups(raft_engine* e, const uint64_t* groups, uint64_t n, int64_t tick0) {
+  if (!e || (n && !groups)) return fail(RAFT_EINVAL, "null argument");
+  const uint64_t G = e->cfg.groups;
+  for (uint64_t i = 0; i < n; ++i)
+    if (groups[i] >= G)
+      return fail(RAFT_ERANGE, "raft_restart_groups: element %llu: group %llu outside the engine's %llu",
+                  (unsigned long long)i, (unsigned long long)groups[i], (unsigned long long)G);
+  if (n)
+    if (int rc = check_distinct(e, groups, sizeof(uint64_t), size_t(n))) return rc;
+  if (int rc = check_ticks(e, tick0, 1)) return rc;
+  if (int rc = settle_check(e)) return rc;
+  if (!n) return RAFT_OK;
+  std::vector<uint32_t> ids(n);
+  for (uint64_t i = 0; i < n; ++i) ids[i] = uint32_t(groups[i]);
+  if (int rc = ensure_stage(e, size_t(n) * 4)) return rc;
+  if (int rc = ring_flush(e)) return rc;
+  host_mutation(e);
+  HIPCHK(hipSetDevice(e->cfg.device));
+  uint32_t* d_ids = static_cast<uint32_t*>(e->stage);
+  HIPCHK(hipMemcpyAsync(d_ids, ids.data(), size_t(n) * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(launch_restart(e->R, e->P, make_trace(e, tick0), d_ids, uint32_t(n), e->feed_mask ? e->feed_cur : nullptr,
+                        e->feed_nm, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return RAFT_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -1,0 +1,249 @@
+// k_groups.hip — the group directory (raft_group_scan, raft_store_groups,
+// raft_restart_groups): find groups by their fault code or lack of a leader,
+// read the canonical view of a list of groups, restart listed groups.
+//
+// Scan: count, scan, emit, like the commit feed (k_feed.hip); no block waits
+// for another.
+//   group_count_kernel<R>  one lane per group decides hit or not from gmeta's
+//        fault field and the R role words of the group's record (the rows
+//        raft_store_state reports: gmeta's primary field is not read, it names
+//        a leader only under STEADY / ONECAND / ONESTALE) and writes the
+//        block's number of hits;
+//   feed_scan_kernel       (k_feed.hip) the exclusive scan of the block sums
+//        and the total;
+//   group_emit_kernel<R>   every block below the cap decides again, places
+//        its hits by ballot and prefix inside the wave (consecutive hits are
+//        consecutive 16-B records) and the lane that writes the last record
+//        stores the id after it.
+// Gather: the canonical view of ids[0..n) into a staging buffer in the view's
+// layout, derived as digest_kernel derives it (gmeta, gss / glx or the planes,
+// max(hwm plane, last) under MSYNC, ring_slot over the three phase segments,
+// shared entries from the shared ring): one lane per listed group for the
+// scalars and the match / next rows, one wave per listed group for the logs.
+// Restart: init_new_group (tick_common.hpp) for g = ids[i], feed cursors to 0.
+#include "tick_common.hpp"
+
+namespace raftstep {
+
+namespace {
+
+// Is group g a hit, and the lowest-id replica whose State is Leader (0xFF: none).
+template <int R>
+__device__ __forceinline__ bool group_hit(const DevPlanes& P, uint32_t g, uint32_t select, uint32_t* fault,
+                                          uint32_t* leader) {
+  const uint32_t f = (uint32_t(at(P.gmeta, g)) >> 4) & 7u;
+  uint32_t ld = 0xFFu;
+#pragma unroll
+  for (int r = R - 1; r >= 0; --r)
+    if ((uint32_t(at(P.rs, rix<R>(g, r))) & 3u) == uint32_t(ROLE_L)) ld = uint32_t(r);
+  *fault = f;
+  *leader = ld;
+  return ((select & 1u) && f != 0u) || ((select & 2u) && f == 0u && ld == 0xFFu);
+}
+
+}  // namespace
+
+// Blocks cover groups from block b0 = first / 256 on; groups below `first` are no hits.
+template <int R>
+__global__ __launch_bounds__(256) void group_count_kernel(DevPlanes P, uint32_t select, uint32_t first, uint32_t b0,
+                                                          uint32_t* bsum) {
+  __shared__ uint32_t s_w[4];
+  const uint32_t g = (b0 + blockIdx.x) * 256u + threadIdx.x;
+  bool hit = false;
+  if (g < P.G && g >= first) {
+    uint32_t f, ld;
+    hit = group_hit<R>(P, g, select, &f, &ld);
+  }
+  const uint32_t n = uint32_t(__popcll(__ballot(hit)));
+  if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) bsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// cap >= 1: the records this scan writes (min of the caller's cap and the
+// total); hit p of the ascending group order is written iff p < cap, and the
+// lane that writes hit cap - 1 stores its group's id + 1 to *next.
+template <int R>
+__global__ __launch_bounds__(256) void group_emit_kernel(DevPlanes P, uint32_t select, uint32_t first, uint32_t b0,
+                                                         const uint64_t* boff, uint64_t cap, uint32_t* out,
+                                                         unsigned long long* next) {
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  __shared__ uint32_t s_w[4];
+  const uint64_t base = boff[blockIdx.x];
+  if (base >= cap) return;   // (the whole block: nothing of it is written)
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t g = (b0 + blockIdx.x) * 256u + threadIdx.x;
+  bool hit = false;
+  uint32_t f = 0, ld = 0xFFu;
+  if (g < P.G && g >= first) hit = group_hit<R>(P, g, select, &f, &ld);
+  const unsigned long long b = __ballot(hit);
+  if (lane == 0) s_w[wave] = uint32_t(__popcll(b));
+  __syncthreads();
+  uint64_t pos = base + uint32_t(__popcll(b & ((1ull << lane) - 1ull)));
+  for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
+  if (!hit || pos >= cap) return;
+  const uint64_t gid = P.gbase + g;
+  // raft_group_hit: group, local, fault | leader << 8 | reserved 0
+  reinterpret_cast<u4*>(out)[pos] = u4{uint32_t(gid), uint32_t(gid >> 32), g, f | (ld << 8)};
+  if (pos == cap - 1) *next = uint64_t(g) + 1u;
+}
+
+// The scalars and the match / next rows of listed group i < n, one lane each.
+template <int R>
+__global__ __launch_bounds__(256) void gather_scalar_kernel(DevPlanes P, int raft, const uint32_t* ids, uint32_t n,
+                                                            GatherOut o) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t g = ids[i];
+  const int meta = at(P.gmeta, g);
+  const int primary = meta & 0xF, fault = (meta >> 4) & 7;
+  const bool msync = (meta & M_MSYNC) && primary < R;
+  const bool ssync = (meta & M_SSYNC) && primary < R;   // compressed state: the gss record
+  const SsRec ss = ssync ? P.gss[g] : SsRec{0, 0, 0, 0};
+  const LxRec lx = (ssync && uses_glx(meta)) ? P.glx[g] : LxRec{0, 0};
+  const int hb = (P.sh && (at(P.grot, g) & ROT_SH)) ? P.sh_hb : at(P.hb, g);   // (SH: implied)
+  int last[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) last[r] = ssync ? ss_last(ss, r, primary, meta, lx) : at(P.last, rix<R>(g, r));
+  if (o.fault) o.fault[i] = uint8_t(fault);
+  if (o.iso_victim) o.iso_victim[i] = uint8_t(at(P.giso, g));
+#pragma unroll 1
+  for (int r = 0; r < R; ++r) {
+    const uint32_t x = at(P.rs, rix<R>(g, r));
+    const int role = int(x & 3u), dur = int(x >> 6);
+    const int l = sel(last, r);
+    const int ts = at(P.tstart, rix<R>(g, r));
+    const uint32_t c = i * uint32_t(R) + uint32_t(r);
+    if (o.role) o.role[c] = uint8_t(role);
+    if (o.voted) o.voted[c] = uint8_t((x >> 2) & 15u);
+    if (o.term) o.term[c] = ssync ? ss_term(ss, r, meta, lx) : at(P.term, rix<R>(g, r));
+    if (o.last) o.last[c] = l;
+    if (o.commit) {
+      const int pc = at(P.commit, rix<R>(g, r));
+      o.commit[c] = ssync ? ss_commit(ss, r, primary, meta, lx, pc) : pc;
+    }
+    // deadline = effective timer start + d; followers / candidates also count the heartbeat
+    if (o.deadline) o.deadline[c] = (role == ROLE_L ? ts : max(ts, hb)) + dur;
+    if (o.timeout) o.timeout[c] = dur;
+    // MSYNC: max(plane, LastApplied) (HWX), as the digest reads it
+    if (o.hwm) o.hwm[c] = raft ? (msync ? max(at(P.hwm, rix<R>(g, r)), l) : at(P.hwm, rix<R>(g, r))) : l;
+    if (o.match || o.next) {
+#pragma unroll 1
+      for (int p = 0; p < R; ++p) {
+        int m = 0, nx = 0;
+        if (role == ROLE_L && p != r) {
+          const int lp = sel(last, p);
+          const bool mp = msync && msync_peer(meta, lx, p);   // (SXS: the stale leader's row is explicit)
+          if (r == primary) m = mp ? lp : at(P.lmatch, rix<R>(g, p));
+          else m = at(prow(P.xmatch, r * R + p, P.Gp), g);
+          if (!raft) nx = m + 1;
+          else if (r == primary) nx = mp ? lp + 1 : at(P.lnext, rix<R>(g, p));
+          else nx = at(prow(P.xnext, r * R + p, P.Gp), g);
+        }
+        if (o.match) o.match[size_t(c) * R + p] = m;
+        if (o.next) o.next[size_t(c) * R + p] = nx;
+      }
+    }
+  }
+}
+
+// The log fields of listed groups, one wave per group: lane j of a pass is
+// (replica, slot) = (j / K, j % K), so the wave writes output rows
+// [(i R + r) K + s] contiguously; the reads are scattered over the group's
+// ring tile (its R-word runs, 64 R words apart). Slot s holds the largest
+// index idx <= last with (idx - 1) mod K == s, live when idx > max(0, hwm - K).
+template <int R>
+__global__ __launch_bounds__(256) void gather_log_kernel(DevPlanes P, int raft, const uint32_t* ids, uint32_t n,
+                                                         GatherOut o) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (i >= n) return;   // (wave-uniform)
+  const uint32_t g = ids[i];
+  const int meta = at(P.gmeta, g);
+  const int primary = meta & 0xF;
+  const bool msync = (meta & M_MSYNC) && primary < R;
+  const bool ssync = (meta & M_SSYNC) && primary < R;
+  const SsRec ss = ssync ? P.gss[g] : SsRec{0, 0, 0, 0};
+  const LxRec lx = (ssync && uses_glx(meta)) ? P.glx[g] : LxRec{0, 0};
+  const uint32_t rot = at(P.grot, g), rota = at(P.grota, g), rotb = at(P.grotb, g);
+  const int sb = at(P.gsb, g), sb2 = at(P.gsb2, g);
+  // SH (ROT_SH): entries from shf on are read from the shared ring
+  const int shf = (P.sh && (rot & ROT_SH)) ? at(P.gshf, g) : 2147483647;
+  const uint64_t rb = ring_tile(g, P.KP, R), shb = sh_tile(g, P.KP);
+  const uint32_t K = P.K, RK = uint32_t(R) * K;
+  const size_t ob = size_t(i) * RK;
+  for (uint32_t j = lane; j < RK; j += 64u) {
+    const uint32_t r = j / K, s = j & (K - 1u);
+    const int l = ssync ? ss_last(ss, int(r), primary, meta, lx) : at(P.last, rix<R>(g, int(r)));
+    const int hwm = raft ? (msync ? max(at(P.hwm, rix<R>(g, int(r))), l) : at(P.hwm, rix<R>(g, int(r)))) : l;
+    const int idx = l >= 1 ? l - int(uint32_t(l - 1 - int(s)) & (K - 1u)) : 0;
+    const bool live = idx >= 1 && idx > hwm - int(K);
+    int32_t lt = 0;
+    int64_t lv = 0;
+    uint32_t lc = 0;
+    if (live) {
+      const uint32_t slot = ring_slot(idx, rot, rota, rotb, sb, sb2, P.kmask);
+      if (idx >= shf) {
+        const uint32_t so = sh_in_tile(g, slot, P.sh_cs);
+        if (o.log_term) lt = at(P.sh_term + shb, so);
+        if (o.log_value) lv = at(P.sh_value + shb, so);
+        if (o.log_crc && P.crc_on) lc = at(P.sh_crc + shb, so);
+      } else {
+        const uint32_t q = ring_in_tile(g, R, slot, r);
+        if (o.log_term) lt = at(P.log_term + rb, q);
+        if (o.log_value) lv = at(P.log_value + rb, q);
+        if (o.log_crc && P.crc_on) lc = at(P.log_crc + rb, q);
+      }
+    }
+    if (o.log_term) o.log_term[ob + j] = lt;
+    if (o.log_value) o.log_value[ob + j] = lv;
+    if (o.log_crc) o.log_crc[ob + j] = lc;
+  }
+}
+
+// NewNode x R for the listed groups (distinct ids); cur (may be null): the
+// commit feed's cursors [G][nm], the listed groups' become 0 =
+// min(CommitIndex, LastApplied) of the new state.
+template <int R>
+__global__ __launch_bounds__(256) void restart_kernel(DevPlanes P, Trace T, const uint32_t* ids, uint32_t n, int32_t* cur,
+                                                      uint32_t nm) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t g = ids[i];
+  init_new_group<R>(P, T, g);
+  if (cur)
+    for (uint32_t k = 0; k < nm; ++k) cur[size_t(g) * nm + k] = 0;
+}
+
+hipError_t launch_group_count(int R, const DevPlanes& P, uint32_t select, uint32_t first, uint32_t* bsum, hipStream_t s) {
+  const uint32_t b0 = first >> 8, nb = uint32_t((P.G + 255) / 256) - b0;
+  RAFT_DISPATCH_R(R, hipLaunchKernelGGL(group_count_kernel<RR>, dim3(nb), dim3(256), 0, s, P, select, first, b0, bsum));
+  return hipGetLastError();
+}
+hipError_t launch_group_emit(int R, const DevPlanes& P, uint32_t select, uint32_t first, const uint64_t* boff,
+                             uint64_t cap, void* out, unsigned long long* next, hipStream_t s) {
+  const uint32_t b0 = first >> 8, nb = uint32_t((P.G + 255) / 256) - b0;
+  RAFT_DISPATCH_R(R, hipLaunchKernelGGL(group_emit_kernel<RR>, dim3(nb), dim3(256), 0, s, P, select, first, b0, boff, cap,
+                                        static_cast<uint32_t*>(out), next));
+  return hipGetLastError();
+}
+hipError_t launch_gather(int R, const DevPlanes& P, int raft, const uint32_t* ids, uint32_t n, const GatherOut& o,
+                         hipStream_t s) {
+  const bool scalars = o.role || o.voted || o.term || o.last || o.commit || o.deadline || o.timeout || o.match ||
+                       o.fault || o.next || o.hwm || o.iso_victim;
+  if (scalars) {
+    RAFT_DISPATCH_R(R, hipLaunchKernelGGL(gather_scalar_kernel<RR>, grid_for(n), dim3(256), 0, s, P, raft, ids, n, o));
+    if (hipError_t rc = hipGetLastError()) return rc;
+  }
+  if (o.log_term || o.log_value || o.log_crc) {   // (no log pointer: no ring word is read)
+    RAFT_DISPATCH_R(R, hipLaunchKernelGGL(gather_log_kernel<RR>, dim3((n + 3u) / 4u), dim3(256), 0, s, P, raft, ids, n, o));
+  }
+  return hipGetLastError();
+}
+hipError_t launch_restart(int R, const DevPlanes& P, const Trace& T, const uint32_t* ids, uint32_t n, int32_t* cursors,
+                          uint32_t nm, hipStream_t s) {
+  RAFT_DISPATCH_R(R, hipLaunchKernelGGL(restart_kernel<RR>, grid_for(n), dim3(256), 0, s, P, T, ids, n, cursors, nm));
+  return hipGetLastError();
+}
+
+}  // namespace raftstep

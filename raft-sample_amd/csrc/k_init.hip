@@ -9,26 +9,7 @@ template <int R>
 __global__ __launch_bounds__(256) void init_new_kernel(DevPlanes P, Trace T) {
   const uint64_t g = uint64_t(blockIdx.x) * 256u + threadIdx.x;
   if (g >= P.G) return;
-  const uint64_t key = group_key(T.seed, P.gbase + g);
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const uint32_t i = rix<R>(uint32_t(g), r);   // group record (rix)
-    const int d = T.f_min + int(uint32_t(rng_k(key, r, ST_TIMER_F, uint64_t(T.tick)) >> 32) % uint32_t(T.f_span));
-    P.term[i] = 0; P.last[i] = 0; P.commit[i] = 0;
-    P.tstart[i] = T.now;
-    P.rs[i] = int32_t(ROLE_F | (uint32_t(d) << 6));   // vote 0 (REF: not voted; RAFT: votedFor none)
-    P.lterm[i] = 0;
-    P.lmatch[i] = 0;
-    if (P.hwm) P.hwm[i] = 0;
-  }
-  P.hb[g] = HB_NONE;
-  P.gmeta[g] = uint16_t(NO_PRIMARY);
-  P.giso[g] = 0;
-  P.grot[g] = 0;   // empty logs: the phase is chosen at the first append
-  P.grota[g] = 0;
-  P.gsb[g] = 0;
-  P.grotb[g] = 0;
-  P.gsb2[g] = 0;
+  init_new_group<R>(P, T, g);
 }
 
 // Post-election state (KAT-1 generalised).

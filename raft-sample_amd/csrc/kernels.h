@@ -203,6 +203,37 @@ hipError_t launch_feed_scan(const uint32_t* bsum, uint64_t* boff, uint32_t nb, u
                             unsigned long long* res, hipStream_t s);
 hipError_t launch_feed_emit(int R, const DevPlanes& P, int raft, uint32_t mask, uint32_t nm, int32_t* cursors,
                             const uint64_t* boff, uint64_t cap, void* out, int paired, hipStream_t s);
+// Group directory (k_groups.hip; raft_group_scan / raft_store_groups /
+// raft_restart_groups). select: enum raft_group_select; the launches cover the
+// 256-group blocks from the one holding `first` on (nb = ceil(G / 256) -
+// first / 256 block sums; first < G).
+// launch_group_count: per block its hits in [first, G) (bsum).
+// launch_group_emit: hits [0, cap) of the ascending group order to `out`
+// (16 B each, raft_group_hit), cap >= 1 and at most the total (boff: the
+// exclusive scan of bsum, launch_feed_scan); *next = the local id after hit
+// cap - 1.
+hipError_t launch_group_count(int R, const DevPlanes& P, uint32_t select, uint32_t first, uint32_t* bsum, hipStream_t s);
+hipError_t launch_group_emit(int R, const DevPlanes& P, uint32_t select, uint32_t first, const uint64_t* boff,
+                             uint64_t cap, void* out, unsigned long long* next, hipStream_t s);
+// The canonical view (raft_state_view's fields and shapes, indexed by list
+// position) of groups ids[0..n) into device buffers; null fields are skipped,
+// and without a log field no ring word is read.
+struct GatherOut {
+  uint8_t *role, *voted;
+  int32_t *term, *last, *commit, *deadline, *timeout, *match;
+  uint8_t* fault;
+  int32_t* log_term;
+  int64_t* log_value;
+  uint32_t* log_crc;
+  int32_t *next, *hwm;
+  uint8_t* iso_victim;
+};
+hipError_t launch_gather(int R, const DevPlanes& P, int raft, const uint32_t* ids, uint32_t n, const GatherOut& o,
+                         hipStream_t s);
+// NewNode x R (init_new_group) for the distinct groups ids[0..n); cursors (may
+// be null): the open commit feed's, [G][nm], set to 0 for those groups.
+hipError_t launch_restart(int R, const DevPlanes& P, const Trace& T, const uint32_t* ids, uint32_t n, int32_t* cursors,
+                          uint32_t nm, hipStream_t s);
 hipError_t launch_stream_probe(int R, const uint16_t* a, SsRec* b, const uint16_t* c, int32_t* d, int32_t* rt,
                                int64_t* rv, uint32_t n, uint32_t slot, uint32_t kslots, hipStream_t s,
                                uint32_t mode = 0);

@@ -246,6 +246,33 @@ __device__ __forceinline__ void with_replica(int x, F&& f) {
   });
 }
 
+// NewNode (main.go:59-76) + FollowerRun entry (main.go:113-115) for every
+// replica of group g: what raft_init_new_nodes writes for it, and
+// raft_restart_groups for a listed group (k_init.hip, k_groups.hip).
+template <int R>
+__device__ __forceinline__ void init_new_group(const DevPlanes& P, const Trace& T, uint64_t g) {
+  const uint64_t key = group_key(T.seed, P.gbase + g);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const uint32_t i = rix<R>(uint32_t(g), r);   // group record (rix)
+    const int d = T.f_min + int(uint32_t(rng_k(key, r, ST_TIMER_F, uint64_t(T.tick)) >> 32) % uint32_t(T.f_span));
+    P.term[i] = 0; P.last[i] = 0; P.commit[i] = 0;
+    P.tstart[i] = T.now;
+    P.rs[i] = int32_t(ROLE_F | (uint32_t(d) << 6));   // vote 0 (REF: not voted; RAFT: votedFor none)
+    P.lterm[i] = 0;
+    P.lmatch[i] = 0;
+    if (P.hwm) P.hwm[i] = 0;
+  }
+  P.hb[g] = HB_NONE;
+  P.gmeta[g] = uint16_t(NO_PRIMARY);
+  P.giso[g] = 0;
+  P.grot[g] = 0;   // empty logs: the phase is chosen at the first append
+  P.grota[g] = 0;
+  P.gsb[g] = 0;
+  P.grotb[g] = 0;
+  P.gsb2[g] = 0;
+}
+
 #define RAFT_DISPATCH_R(R_, CALL)                                              \
   switch (R_) {                                                                \
     case 1: { constexpr int RR = 1; CALL; } break;                             \

@@ -192,11 +192,23 @@ class FeedInfo(C.Structure):
     _fields_ = [("delivered", C.c_uint64), ("pending", C.c_uint64), ("lost", C.c_uint64), ("stalled", C.c_uint64)]
 
 
+# group directory (raft_group_hit / raft_scan_info / enum raft_group_select)
+GROUP_HIT = np.dtype([("group", "<u8"), ("local", "<u4"), ("fault", "u1"), ("leader", "u1"), ("reserved", "<u2")],
+                     align=True)
+SELECT_FAULTED, SELECT_LEADERLESS = 1, 2
+NO_LEADER = 0xFF   # raft_group_hit.leader: no replica's State is Leader
+
+
+class ScanInfo(C.Structure):
+    _fields_ = [("matched", C.c_uint64), ("written", C.c_uint64), ("next_group", C.c_uint64)]
+
+
 assert AE_REQ.itemsize == 64 and AE_RESP.itemsize == 24 and LOG_ENTRY.itemsize == 16
 assert VOTE_REQ.itemsize == 40 and VOTE_RESP.itemsize == 16
 assert GROUP_OP.itemsize == 24 and OP_RESULT.itemsize == 16
 assert C.sizeof(Config) == 120, C.sizeof(Config)
 assert FEED_ENTRY.itemsize == 32 and C.sizeof(FeedInfo) == 32
+assert GROUP_HIT.itemsize == 16 and C.sizeof(ScanInfo) == 24
 
 # exported symbols of libraftstep.so (the C-ABI), with ctypes signatures
 P = C.c_void_p
@@ -240,14 +252,18 @@ SIGNATURES = {
     "raft_feed_poll": (C.c_int, [P, P, C.c_uint64, P]),
     "raft_feed_cursors": (C.c_int, [P, P]),
     "raft_feed_close": (C.c_int, [P]),
+    "raft_group_scan": (C.c_int, [P, C.c_uint32, C.c_uint64, P, C.c_uint64, P]),
+    "raft_store_groups": (C.c_int, [P, P, C.c_uint64, P]),
+    "raft_restart_groups": (C.c_int, [P, P, C.c_uint64, C.c_int64]),
 }
 
 
 # measurement / diagnostics entry points added in round 5: an older build
 # loaded through RAFTSTEP_LIB (A/B runs) may lack them
-# (and the commit feed, added later still)
+# (and the commit feed and the group directory, added later still)
 OPTIONAL = ("raft_debug_diag_mode", "raft_stream_probe", "raft_engine_features",
-            "raft_feed_open", "raft_feed_poll", "raft_feed_cursors", "raft_feed_close")
+            "raft_feed_open", "raft_feed_poll", "raft_feed_cursors", "raft_feed_close",
+            "raft_group_scan", "raft_store_groups", "raft_restart_groups")
 FEATURE_SHARED_ENTRIES, FEATURE_VIRTUAL_SUFFIXES = 1, 2   # raft_engine_features (include/raftstep.h)
 PROBE_PLAIN_RING, PROBE_NT_RECORD, PROBE_NO_HEARTBEAT = 1, 2, 4   # raft_stream_probe flags
 

@@ -214,6 +214,45 @@ class Engine:
     def feed_close(self):
         _check(self.lib.raft_feed_close(self.h))
 
+    # -- group directory -----------------------------------------------
+    def group_scan(self, select, first_group=0, cap=None):
+        """Groups in [first_group, G) that are faulted and / or leaderless
+        (raft_group_scan; select: abi.SELECT_* bits): (GROUP_HIT array in
+        ascending group order, info dict with matched, written, next_group).
+        cap=None counts first, then takes every hit."""
+        info = abi.ScanInfo()
+        if cap is None:
+            _check(self.lib.raft_group_scan(self.h, int(select), int(first_group), None, 0, C.byref(info)))
+            cap = info.matched
+        out = np.zeros(int(cap), abi.GROUP_HIT)
+        _check(self.lib.raft_group_scan(self.h, int(select), int(first_group), _ptr(out), int(cap), C.byref(info)))
+        d = {k: int(getattr(info, k)) for k, _ in abi.ScanInfo._fields_}
+        return out[:d["written"]], d
+
+    @staticmethod
+    def _ids(ids):
+        a = np.asarray(ids)
+        if a.ndim != 1 or (a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0)):
+            raise ValueError("group ids: a 1-D array of non-negative integers expected")
+        return np.ascontiguousarray(a, dtype=np.uint64)
+
+    def store_groups(self, ids, logs=True):
+        """Canonical view of the listed groups (local ids, any order, repeats
+        allowed), indexed by list position (raft_store_groups)."""
+        ids = self._ids(ids)
+        st = abi.empty_state(len(ids), self.cfg.replicas, self.cfg.ring_depth)
+        if not logs:
+            for k in ("log_term", "log_value", "log_crc"):
+                st.pop(k)
+        v = abi.make_view(st)
+        _check(self.lib.raft_store_groups(self.h, _ptr(ids), len(ids), C.byref(v)))
+        return st
+
+    def restart_groups(self, ids, tick0):
+        """NewNode x R for the listed (distinct) groups at virtual tick tick0 (raft_restart_groups)."""
+        ids = self._ids(ids)
+        _check(self.lib.raft_restart_groups(self.h, _ptr(ids), len(ids), int(tick0)))
+
     # -- the fused tick ------------------------------------------------
     def tick(self, first_tick, nticks=1, stats=True):
         if stats:

@@ -193,9 +193,10 @@ int raft_load_state(raft_engine* e, const raft_state_view* v);
 int raft_store_state(raft_engine* e, raft_state_view* v);
 /* The canonical view of groups [first_group, first_group + n_groups) only,
  * indexed by the local group (g - first_group) with the same per-group shapes
- * as raft_store_state; copies out only that slice of the device state, so a
- * slice of a multi-million-group engine can be compared with a CPU run of the
- * same groups (RAFT_ERANGE when the range leaves the engine). */
+ * as raft_store_state; the view of that slice alone is derived on the device
+ * and copied out (as for raft_store_state and raft_store_groups), so a slice
+ * of a multi-million-group engine can be compared with a CPU run of the same
+ * groups (RAFT_ERANGE when the range leaves the engine). */
 int raft_store_state_range(raft_engine* e, uint64_t first_group, uint64_t n_groups, raft_state_view* v);
 
 /* ---- audit: digests, nodelog, checkpoints ---------------------------------

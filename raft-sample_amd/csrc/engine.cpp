@@ -578,25 +578,13 @@ int run_ops(raft_engine* e, int64_t now_tick, const std::vector<DevOp>& ops, con
 }
 
 template <typename T>
-int d2h(raft_engine* e, std::vector<T>& h, const T* d, size_t n) {
-  h.resize(n);
-  HIPCHK(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, e->stream));
-  return RAFT_OK;
-}
-template <typename T>
 int h2d(raft_engine* e, T* d, const std::vector<T>& h) {
   HIPCHK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, e->stream));
   return RAFT_OK;
 }
 
-// Group records <-> per-row host arrays [Gp][R] (row k of group g at
+// Per-row host arrays [Gp][R] -> group records (row k of group g at
 // blk[g*recw + k*R ..], raft_device.hpp rix)
-void rec_rows(const std::vector<int32_t>& blk, int k, uint64_t R, uint64_t Gp, std::vector<int32_t>& out) {
-  const uint64_t W = recw_of(uint32_t(R));
-  out.resize(R * Gp);
-  for (uint64_t g = 0; g < Gp; ++g)
-    std::memcpy(&out[g * R], &blk[g * W + uint64_t(k) * R], R * 4);
-}
 void rec_put(std::vector<int32_t>& blk, int k, uint64_t R, uint64_t Gp, const std::vector<int32_t>& rows) {
   const uint64_t W = recw_of(uint32_t(R));
   for (uint64_t g = 0; g < Gp; ++g)
@@ -957,149 +945,89 @@ int raft_init_steady(raft_engine* e, int32_t leader, int64_t tick0) {
 
 namespace {
 
-// Canonical view of groups [g0, g0+n): only that slice of every plane (and
-// the ring tiles holding it) is copied out; the view is indexed by the
-// local group g - g0.
-int store_range(raft_engine* e, uint64_t g0, uint64_t n, raft_state_view* v) {
+// The canonical view's fields, in raft_state_view and checkpoint-file order:
+// name, where the host pointer sits in raft_state_view and the staging pointer
+// in GatherOut, element bytes and elements per group. The one table behind the
+// gather and the checkpoint files.
+struct ViewField {
+  const char* name;
+  size_t host, dev;
+  uint32_t elem;
+  uint64_t per;
+  void*& slot(raft_state_view& v) const { return *reinterpret_cast<void**>(reinterpret_cast<char*>(&v) + host); }
+  void*& slot(GatherOut& o) const { return *reinterpret_cast<void**>(reinterpret_cast<char*>(&o) + dev); }
+  size_t bytes() const { return size_t(elem) * per; }   // per group
+};
+std::vector<ViewField> view_fields(uint64_t R, uint64_t K) {
+#define VIEW_FIELD(f, elem, per) {#f, offsetof(raft_state_view, f), offsetof(GatherOut, f), elem, per}
+  return {VIEW_FIELD(role, 1, R),         VIEW_FIELD(voted, 1, R),         VIEW_FIELD(term, 4, R),
+          VIEW_FIELD(last, 4, R),         VIEW_FIELD(commit, 4, R),        VIEW_FIELD(deadline, 4, R),
+          VIEW_FIELD(timeout, 4, R),      VIEW_FIELD(match, 4, R * R),     VIEW_FIELD(fault, 1, 1),
+          VIEW_FIELD(log_term, 4, R * K), VIEW_FIELD(log_value, 8, R * K), VIEW_FIELD(log_crc, 4, R * K),
+          VIEW_FIELD(next, 4, R * R),     VIEW_FIELD(hwm, 4, R),           VIEW_FIELD(iso_victim, 1, 1)};
+#undef VIEW_FIELD
+}
+
+// The canonical view of n groups, ids[0..n) or with ids null the range
+// [first, first + n), into *v indexed by position: the gather kernels
+// (k_groups.hip, canon_view.hpp) fill raft_engine::stage chunk by chunk and
+// every present field is copied out of it. No entry protocol: the callers
+// (raft_store_state / _range / _groups, raft_nodelog) run their own first.
+// check_lterm (with log_term): RAFT_EINTERNAL when a replica's cached
+// last-entry term differs from its ring's entry at LastApplied.
+int gather_view(raft_engine* e, uint64_t first, const uint32_t* ids, uint64_t n, const raft_state_view* v,
+                bool check_lterm) {
+  if (!n) return RAFT_OK;
   HIPCHK(hipSetDevice(e->cfg.device));
-  const uint64_t R = e->cfg.replicas, Gp = e->Gp, K = e->cfg.ring_depth;
-  const bool raft = e->cfg.semantics == RAFT_SEM_RAFT;
-  std::vector<int32_t> term, last, commit, ts, hb, lm, xm, lt, ln, xn, hw, rs, blk;
-  std::vector<uint16_t> meta, rot, rota, rotb;
-  std::vector<uint8_t> giso;
-  std::vector<int32_t> sb, sb2;
-  std::vector<int64_t> lv;
-  std::vector<uint32_t> lcrc;
-  const uint64_t W = recw_of(uint32_t(R));
-  int rc = RAFT_OK;
-  if (!rc) rc = d2h(e, blk, e->P.rec + g0 * W, n * W);   // group records (rows extracted below)
-  if (!rc) rc = d2h(e, hb, e->P.hb + g0, n);
-  // [R][R][Gp] rows of further leaders: R*R strided slices
-  auto rows2d = [&](std::vector<int32_t>& h, const int32_t* d) -> int {
-    h.resize(R * R * n);
-    HIPCHK(hipMemcpy2DAsync(h.data(), n * 4, d + g0, Gp * 4, n * 4, R * R, hipMemcpyDeviceToHost, e->stream));
-    return RAFT_OK;
-  };
-  if (!rc) rc = rows2d(xm, e->P.xmatch);
-  if (!rc) rc = d2h(e, meta, e->P.gmeta + g0, n);
-  std::vector<GSeg> cold;   // the packed cold words (GSeg), split below
-  if (!rc && (v->iso_victim || v->log_term || v->log_value || v->log_crc)) rc = d2h(e, cold, e->P.gseg + g0, n);
-  if (!rc && v->iso_victim) rc = d2h(e, giso, e->giso_plane + g0, n);
-
-  if (!rc && raft) rc = rows2d(xn, e->P.xnext);
-  const bool logs = v->log_term || v->log_value || v->log_crc;
-  std::vector<int32_t> ltm;
-  const uint64_t KP = e->KP;
-  const uint64_t t0 = g0 >> 6, nt = ((g0 + n - 1) >> 6) - t0 + 1;   // ring tiles [t0, t0+nt)
-  const uint64_t tile = KP * 64 * R;
-  if (!rc && logs) rc = d2h(e, rot, e->P.grot + g0, n);
-  if (!rc && logs) rc = d2h(e, sb, e->P.gsb + g0, n);
-
-  std::vector<SsRec> gss;
-  if (!rc) rc = d2h(e, gss, e->P.gss + g0, n);
-  std::vector<LxRec> glx;
-  if (!rc) rc = d2h(e, glx, e->P.glx + g0, n);
-  if (!rc && logs) rc = d2h(e, lt, e->P.log_term + t0 * tile, nt * tile);
-  if (!rc && logs) rc = d2h(e, lv, e->P.log_value + t0 * tile, nt * tile);
-  const bool crcs = v->log_crc && e->cfg.payload_crc;
-  if (!rc && crcs) rc = d2h(e, lcrc, e->P.log_crc + t0 * tile, nt * tile);
-  if (rc) return rc;
+  const uint64_t R = e->cfg.replicas, K = e->cfg.ring_depth;
+  raft_state_view h = *v;
+  // (without payload_crc the stamps read back as 0: zeroed here, nothing gathered or copied for them)
+  if (h.log_crc && !e->cfg.payload_crc) {
+    std::memset(h.log_crc, 0, size_t(n) * R * K * 4);
+    h.log_crc = nullptr;
+  }
+  const std::vector<ViewField> fields = view_fields(R, K);
+  size_t per = 0;
+  for (const ViewField& f : fields)
+    if (f.slot(h)) per += f.bytes();
+  if (!per) return RAFT_OK;
+  // chunks of groups bound the staging: the ids, the check's word, then each field's rows of one chunk
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const uint64_t chunk = std::min<uint64_t>(n, std::max<uint64_t>(256, (uint64_t(32) << 20) / per));
+  const size_t b_ids = ids ? al(size_t(n) * 4) : 0;
+  size_t need = b_ids + 256;
+  for (const ViewField& f : fields)
+    if (f.slot(h)) need += al(f.bytes() * chunk);
+  if (int rc = ensure_stage(e, need)) return rc;
+  char* base = static_cast<char*>(e->stage);
+  uint32_t* d_ids = reinterpret_cast<uint32_t*>(base);
+  uint32_t* d_bad = (check_lterm && h.log_term) ? reinterpret_cast<uint32_t*>(base + b_ids) : nullptr;
+  GatherOut o{};
+  size_t off = b_ids + 256;
+  for (const ViewField& f : fields) {
+    if (!f.slot(h)) continue;
+    f.slot(o) = base + off;
+    off += al(f.bytes() * chunk);
+  }
+  if (ids) HIPCHK(hipMemcpyAsync(d_ids, ids, size_t(n) * 4, hipMemcpyHostToDevice, e->stream));
+  if (d_bad) HIPCHK(hipMemsetAsync(d_bad, 0, 4, e->stream));
+  const int raft = e->cfg.semantics == RAFT_SEM_RAFT;
+  for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
+    const uint64_t nc = std::min<uint64_t>(chunk, n - c0);
+    // (the stream orders this chunk's kernels after the last chunk's copies out of the same buffers)
+    HIPCHK(launch_gather(e->R, e->P, raft, uint32_t(first + c0), ids ? d_ids + c0 : nullptr, uint32_t(nc), o, d_bad,
+                         e->stream));
+    for (const ViewField& f : fields)
+      if (f.slot(h))
+        HIPCHK(hipMemcpyAsync(static_cast<char*>(f.slot(h)) + c0 * f.bytes(), f.slot(o), nc * f.bytes(),
+                              hipMemcpyDeviceToHost, e->stream));
+  }
+  uint32_t bad = 0;
+  if (d_bad) HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  if (!cold.empty()) {   // (the packed cold words, copied above, split after the copy completed)
-    rota.resize(n);
-    rotb.resize(n);
-    sb2.resize(n);
-    for (uint64_t g = 0; g < n; ++g) {
-      rota[g] = cold[g].rota;
-      rotb[g] = cold[g].rotb;
-      sb2[g] = cold[g].sb2;
-    }
-  }
-  rec_rows(blk, PL_TERM, R, n, term);
-  rec_rows(blk, PL_LAST, R, n, last);
-  rec_rows(blk, PL_COMMIT, R, n, commit);
-  rec_rows(blk, PL_TSTART, R, n, ts);
-  rec_rows(blk, PL_RS, R, n, rs);
-  rec_rows(blk, PL_LMATCH, R, n, lm);
-  if (raft) rec_rows(blk, PL_LNEXT, R, n, ln);
-  if (raft) rec_rows(blk, PL_HWM, R, n, hw);
-  if (logs) rec_rows(blk, PL_LTERM, R, n, ltm);
-  std::vector<int32_t>().swap(blk);
-  // SSYNC groups: the planes are stale, the gss record (+ glx) is the state
-  for (uint64_t g = 0; g < n; ++g) {
-    const int pr = meta[g] & 0xF;
-    if (!(meta[g] & M_SSYNC) || pr >= int(R)) continue;
-    for (uint64_t r = 0; r < R; ++r) {
-      term[g * R + r] = ss_term(gss[g], int(r), meta[g], glx[g]);
-      last[g * R + r] = ss_last(gss[g], int(r), pr, meta[g], glx[g]);
-      commit[g * R + r] = ss_commit(gss[g], int(r), pr, meta[g], glx[g], commit[g * R + r]);
-      if (!ltm.empty()) ltm[g * R + r] = ss_term(gss[g], int(r), meta[g], glx[g]);
-    }
-  }
-  for (uint64_t g = 0; g < n; ++g) {
-    const int primary = meta[g] & 0xF;
-    const bool msync = meta[g] & M_MSYNC;
-    const LxRec lxg = (meta[g] & M_SSYNC) ? glx[g] : LxRec{0, 0};
-    const uint64_t gt = g0 + g - t0 * 64;   // group index inside the copied ring tiles
-    if (v->fault) v->fault[g] = uint8_t((meta[g] >> 4) & 7);
-    if (v->iso_victim) v->iso_victim[g] = giso[g];
-    for (uint64_t r = 0; r < R; ++r) {
-      const uint64_t d = g * R + r, c = g * R + r;   // per-replica planes are group-major (rix)
-      const int role = rs[d] & 3;
-      if (v->role) v->role[c] = uint8_t(role);
-      if (v->voted) v->voted[c] = uint8_t((rs[d] >> 2) & 15);
-      if (v->term) v->term[c] = term[d];
-      if (v->last) v->last[c] = last[d];
-      if (v->commit) v->commit[c] = commit[d];
-      // deadline = effective timer start + d; followers/candidates also count hb
-      if (v->deadline) v->deadline[c] = (role == ROLE_L ? ts[d] : std::max(ts[d], hb[g])) + int32_t(rs[d] >> 6);
-      if (v->timeout) v->timeout[c] = int32_t(rs[d] >> 6);
-      // RAFT + MSYNC: high-water marks and the primary's NextIndex row are implicit too
-      // (MSYNC: max(plane, LastApplied), raft_device.hpp M_HWX)
-      const int32_t hwm = raft ? (msync ? std::max(hw[d], last[d]) : hw[d]) : last[d];
-      if (v->hwm) v->hwm[c] = hwm;
-      if (v->match)
-        for (uint64_t p = 0; p < R; ++p) {
-          int32_t m = 0;
-          if (role == ROLE_L && p != r)
-            m = (int(r) == primary) ? (msync_peer(meta[g], lxg, int(p)) ? last[g * R + p] : lm[g * R + p])
-                                    : xm[(r * R + p) * n + g];
-          v->match[c * R + p] = m;
-        }
-      if (v->next)
-        for (uint64_t p = 0; p < R; ++p) {
-          int32_t nx = 0;
-          if (role == ROLE_L && p != r) {
-            const bool mp = msync_peer(meta[g], lxg, int(p));
-            if (raft) nx = (int(r) == primary) ? (mp ? last[g * R + p] + 1 : ln[g * R + p]) : xn[(r * R + p) * n + g];
-            else nx = ((int(r) == primary) ? (mp ? last[g * R + p] : lm[g * R + p]) : xm[(r * R + p) * n + g]) + 1;
-          }
-          v->next[c * R + p] = nx;
-        }
-      // physical slot of entry idx (raft_device.hpp ring_slot)
-      auto pslot = [&](int64_t idx) {
-        return uint64_t((idx - 1 + (idx >= sb[g] ? rot[g] : (idx >= sb2[g] ? rota[g] : rotb[g]))) & int64_t(KP - 1));
-      };
-      if (logs && last[d] > 0) {
-        const int32_t want = lt[ring_index(r, gt, pslot(last[d]), KP, R)];
-        if (ltm[d] != want)
-          return fail(RAFT_EINTERNAL, "last-entry term cache of group %llu replica %llu is %d, ring says %d",
-                      (unsigned long long)(g0 + g), (unsigned long long)r, ltm[d], want);
-      }
-      if (logs) {
-        const int64_t l = last[d];
-        for (uint64_t s = 0; s < K; ++s) {
-          // slot s holds the largest index i <= l with (i-1) mod K == s
-          int64_t idx = l >= 1 ? l - ((l - 1 - int64_t(s)) & int64_t(K - 1)) : 0;
-          const bool live = idx >= 1 && idx <= l && idx > int64_t(hwm) - int64_t(K);
-          const uint64_t o = live ? ring_index(r, gt, pslot(idx), KP, R) : 0;
-          if (v->log_term) v->log_term[c * K + s] = live ? lt[o] : 0;
-          if (v->log_value) v->log_value[c * K + s] = live ? lv[o] : 0;
-          if (v->log_crc) v->log_crc[c * K + s] = (live && crcs) ? lcrc[o] : 0u;
-        }
-      }
-    }
-  }
+  if (bad)   // ~(g R + r) of the lowest mismatch (k_groups.hip gather_log_kernel)
+    return fail(RAFT_EINTERNAL, "last-entry term cache of group %llu replica %llu differs from the ring's entry",
+                (unsigned long long)(~bad / R), (unsigned long long)(~bad % R));
   return RAFT_OK;
 }
 
@@ -1111,7 +1039,7 @@ int raft_store_state(raft_engine* e, raft_state_view* v) {
   if (!e || !v) return fail(RAFT_EINVAL, "null argument");
   if (int rc = settle_check(e)) return rc;
   if (int rc = ring_flush(e)) return rc;
-  return store_range(e, 0, e->cfg.groups, v);
+  return gather_view(e, 0, nullptr, e->cfg.groups, v, true);
 }
 
 int raft_store_state_range(raft_engine* e, uint64_t first_group, uint64_t n_groups, raft_state_view* v) {
@@ -1121,7 +1049,7 @@ int raft_store_state_range(raft_engine* e, uint64_t first_group, uint64_t n_grou
                 (unsigned long long)n_groups, (unsigned long long)e->cfg.groups);
   if (int rc = settle_check(e)) return rc;
   if (int rc = ring_flush(e)) return rc;
-  return store_range(e, first_group, n_groups, v);
+  return gather_view(e, first_group, nullptr, n_groups, v, true);
 }
 
 int raft_load_state(raft_engine* e, const raft_state_view* v) {
@@ -2419,33 +2347,19 @@ int raft_nodelog(raft_engine* e, uint64_t group, char* buf, size_t cap) {
   if (!e || (!buf && cap)) return fail(RAFT_EINVAL, "null argument");
   if (group >= e->cfg.groups) return fail(RAFT_EINVAL, "group %llu out of range", (unsigned long long)group);
   if (int rc = settle_check(e)) return rc;
-  HIPCHK(hipSetDevice(e->cfg.device));
   static const char* names[] = {"follower", "candidate", "leader", "?"};   // State (main.go:51-57)
+  uint8_t role[8];
+  int32_t term[8], commit[8], last[8];
+  raft_state_view v{};
+  v.role = role;
+  v.term = term;
+  v.commit = commit;
+  v.last = last;
+  if (int rc = gather_view(e, group, nullptr, 1, &v, false)) return rc;
   std::string out;
-  uint16_t meta = 0;
-  SsRec ss{};
-  LxRec lx{};
-  HIPCHK(hipMemcpyAsync(&meta, e->P.gmeta + group, 2, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(&ss, e->P.gss + group, sizeof ss, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(&lx, e->P.glx + group, sizeof lx, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  const int pr = meta & 0xF;
-  const bool ssync = (meta & M_SSYNC) && pr < int(e->cfg.replicas);   // compressed state
   for (uint32_t r = 0; r < e->cfg.replicas; ++r) {
-    const uint64_t d = group * recw_of(e->cfg.replicas) + r;   // group record (rix)
-    int32_t term = 0, commit = 0, last = 0, rs = 0;
-    HIPCHK(hipMemcpyAsync(&term, e->P.term + d, 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(&commit, e->P.commit + d, 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(&last, e->P.last + d, 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(&rs, e->P.rs + d, 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (ssync) {
-      term = ss_term(ss, int(r), meta, lx);
-      last = ss_last(ss, int(r), pr, meta, lx);
-      commit = ss_commit(ss, int(r), pr, meta, lx, commit);
-    }
     char line[128];
-    snprintf(line, sizeof line, "[Server%u:%d:%d:%d][%s]\n", r, term, commit, last, names[rs & 3]);
+    snprintf(line, sizeof line, "[Server%u:%d:%d:%d][%s]\n", r, term[r], commit[r], last[r], names[role[r] & 3]);
     out += line;
   }
   if (out.size() + 1 > cap) return fail(RAFT_ERANGE, "nodelog needs %zu bytes", out.size() + 1);
@@ -2695,7 +2609,7 @@ int raft_group_scan(raft_engine* e, uint32_t select, uint64_t first_group, raft_
 
 int raft_store_groups(raft_engine* e, const uint64_t* groups, uint64_t n, raft_state_view* v) {
   if (!e || !v || (n && !groups)) return fail(RAFT_EINVAL, "null argument");
-  const uint64_t G = e->cfg.groups, R = e->cfg.replicas, K = e->cfg.ring_depth;
+  const uint64_t G = e->cfg.groups;
   std::vector<uint32_t> ids(n);
   for (uint64_t i = 0; i < n; ++i) {
     if (groups[i] >= G)
@@ -2704,63 +2618,7 @@ int raft_store_groups(raft_engine* e, const uint64_t* groups, uint64_t n, raft_s
     ids[i] = uint32_t(groups[i]);
   }
   if (int rc = directory_read_begin(e)) return rc;
-  if (!n) return RAFT_OK;
-  // (without payload_crc the stamps read back as 0: zeroed here, nothing gathered or copied for them)
-  uint32_t* const crc_rows = e->cfg.payload_crc ? v->log_crc : nullptr;
-  if (v->log_crc && !crc_rows) std::memset(v->log_crc, 0, size_t(n) * R * K * 4);
-  // the view's fields: host pointer, the staging pointer's slot in GatherOut, bytes per group
-  GatherOut o{};
-  struct Field { void* host; void** dev; size_t per; };
-  const Field fields[] = {
-      {v->role, reinterpret_cast<void**>(&o.role), R},
-      {v->voted, reinterpret_cast<void**>(&o.voted), R},
-      {v->term, reinterpret_cast<void**>(&o.term), R * 4},
-      {v->last, reinterpret_cast<void**>(&o.last), R * 4},
-      {v->commit, reinterpret_cast<void**>(&o.commit), R * 4},
-      {v->deadline, reinterpret_cast<void**>(&o.deadline), R * 4},
-      {v->timeout, reinterpret_cast<void**>(&o.timeout), R * 4},
-      {v->match, reinterpret_cast<void**>(&o.match), R * R * 4},
-      {v->fault, reinterpret_cast<void**>(&o.fault), 1},
-      {v->log_term, reinterpret_cast<void**>(&o.log_term), R * K * 4},
-      {v->log_value, reinterpret_cast<void**>(&o.log_value), R * K * 8},
-      {crc_rows, reinterpret_cast<void**>(&o.log_crc), R * K * 4},
-      {v->next, reinterpret_cast<void**>(&o.next), R * R * 4},
-      {v->hwm, reinterpret_cast<void**>(&o.hwm), R * 4},
-      {v->iso_victim, reinterpret_cast<void**>(&o.iso_victim), 1},
-  };
-  size_t per = 0;
-  for (const Field& f : fields)
-    if (f.host) per += f.per;
-  if (!per) return RAFT_OK;
-  // chunks of groups bound the staging: the ids, then each field's rows of one chunk
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const uint64_t chunk = std::min<uint64_t>(n, std::max<uint64_t>(256, (uint64_t(32) << 20) / per));
-  const size_t b_ids = al(size_t(n) * 4);
-  size_t need = b_ids;
-  for (const Field& f : fields)
-    if (f.host) need += al(f.per * chunk);
-  if (int rc = ensure_stage(e, need)) return rc;
-  char* base = static_cast<char*>(e->stage);
-  uint32_t* d_ids = reinterpret_cast<uint32_t*>(base);
-  size_t off = b_ids;
-  for (const Field& f : fields) {
-    if (!f.host) continue;
-    *f.dev = base + off;
-    off += al(f.per * chunk);
-  }
-  HIPCHK(hipMemcpyAsync(d_ids, ids.data(), size_t(n) * 4, hipMemcpyHostToDevice, e->stream));
-  const int raft = e->cfg.semantics == RAFT_SEM_RAFT;
-  for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
-    const uint64_t nc = std::min<uint64_t>(chunk, n - c0);
-    // (the stream orders this chunk's kernels after the last chunk's copies out of the same buffers)
-    HIPCHK(launch_gather(e->R, e->P, raft, d_ids + c0, uint32_t(nc), o, e->stream));
-    for (const Field& f : fields)
-      if (f.host)
-        HIPCHK(hipMemcpyAsync(static_cast<char*>(f.host) + c0 * f.per, *f.dev, nc * f.per, hipMemcpyDeviceToHost,
-                              e->stream));
-  }
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return RAFT_OK;
+  return gather_view(e, 0, ids.data(), n, v, false);
 }
 
 // Host-side state: the handler batches' route (settle_check, ring_flush,
@@ -2831,31 +2689,6 @@ struct CkptField {   // followed by count * elem bytes
   uint64_t count;
 };
 
-// The canonical view's fields in file order.
-struct ViewField {
-  const char* name;
-  void** ptr;
-  uint32_t elem;
-  uint64_t count;
-};
-std::vector<ViewField> view_fields(raft_state_view& v, uint64_t G, uint64_t R, uint64_t K) {
-  return {{"role", reinterpret_cast<void**>(&v.role), 1, G * R},
-          {"voted", reinterpret_cast<void**>(&v.voted), 1, G * R},
-          {"term", reinterpret_cast<void**>(&v.term), 4, G * R},
-          {"last", reinterpret_cast<void**>(&v.last), 4, G * R},
-          {"commit", reinterpret_cast<void**>(&v.commit), 4, G * R},
-          {"deadline", reinterpret_cast<void**>(&v.deadline), 4, G * R},
-          {"timeout", reinterpret_cast<void**>(&v.timeout), 4, G * R},
-          {"match", reinterpret_cast<void**>(&v.match), 4, G * R * R},
-          {"fault", reinterpret_cast<void**>(&v.fault), 1, G},
-          {"log_term", reinterpret_cast<void**>(&v.log_term), 4, G * R * K},
-          {"log_value", reinterpret_cast<void**>(&v.log_value), 8, G * R * K},
-          {"log_crc", reinterpret_cast<void**>(&v.log_crc), 4, G * R * K},
-          {"next", reinterpret_cast<void**>(&v.next), 4, G * R * R},
-          {"hwm", reinterpret_cast<void**>(&v.hwm), 4, G * R},
-          {"iso_victim", reinterpret_cast<void**>(&v.iso_victim), 1, G}};
-}
-
 struct File {
   FILE* f = nullptr;
   ~File() {
@@ -2871,11 +2704,11 @@ int raft_checkpoint_save(raft_engine* e, const char* path) {
   if (!e || !path) return fail(RAFT_EINVAL, "null argument");
   const uint64_t G = e->cfg.groups, R = e->cfg.replicas, K = e->cfg.ring_depth;
   raft_state_view v{};
-  auto fields = view_fields(v, G, R, K);
+  const auto fields = view_fields(R, K);
   std::vector<std::vector<uint8_t>> bufs(fields.size());
   for (size_t i = 0; i < fields.size(); ++i) {
-    bufs[i].assign(fields[i].count * fields[i].elem, 0);
-    *fields[i].ptr = bufs[i].data();
+    bufs[i].assign(G * fields[i].bytes(), 0);
+    fields[i].slot(v) = bufs[i].data();
   }
   if (int rc = raft_store_state(e, &v)) return rc;
   // written to <path>.tmp, flushed to disk, then renamed over <path>: a crash
@@ -2899,7 +2732,7 @@ int raft_checkpoint_save(raft_engine* e, const char* path) {
     CkptField fh{};
     std::strncpy(fh.name, fields[i].name, sizeof fh.name - 1);
     fh.elem = fields[i].elem;
-    fh.count = fields[i].count;
+    fh.count = G * fields[i].per;
     ok = put(&fh, sizeof fh) && put(bufs[i].data(), bufs[i].size());
   }
   ok = ok && fwrite(&crc, 1, 4, f.f) == 4;
@@ -2963,7 +2796,7 @@ int raft_checkpoint_load(raft_engine* e, const char* path) {
     if (bad) return fail(RAFT_EINVAL, "%s: checkpoint %s differs from this engine's (trace would diverge)", path, bad);
   }
   raft_state_view v{};
-  auto fields = view_fields(v, G, R, K);
+  auto fields = view_fields(R, K);
   if (h.version == 1) fields.pop_back();   // iso_victim: absent (loads as 0)
   if (h.nfields != fields.size()) return fail(RAFT_EINVAL, "%s: %u fields, expected %zu", path, h.nfields, fields.size());
   std::vector<std::vector<uint8_t>> bufs(fields.size());
@@ -2971,12 +2804,12 @@ int raft_checkpoint_load(raft_engine* e, const char* path) {
     CkptField fh{};
     if (!get(&fh, sizeof fh)) return fail(RAFT_EINVAL, "%s: truncated", path);
     if (std::strncmp(fh.name, fields[i].name, sizeof fh.name) != 0 || fh.elem != fields[i].elem ||
-        fh.count != fields[i].count)
+        fh.count != G * fields[i].per)
       return fail(RAFT_EINVAL, "%s: field %zu is %.12s[%llu x %u], expected %s", path, i, fh.name,
                   (unsigned long long)fh.count, fh.elem, fields[i].name);
     bufs[i].resize(fh.count * fh.elem);
     if (!get(bufs[i].data(), bufs[i].size())) return fail(RAFT_EINVAL, "%s: truncated", path);
-    *fields[i].ptr = bufs[i].data();
+    fields[i].slot(v) = bufs[i].data();
   }
   const uint32_t want = crc;
   uint32_t stored = 0;

@@ -4,8 +4,8 @@
 //
 // Three launches per poll, none of which waits for another block:
 //   feed_count_kernel<R>  one lane per group derives (lo, hi] of every masked
-//        replica from the canonical view (as digest_kernel reads it: gmeta,
-//        the gss / glx records or the planes, hwm, the cursor), moves cursors
+//        replica from the canonical view (canon_view.hpp: last, commit, hwm)
+//        and the cursor, moves cursors
 //        past entries that left the ring (`lost`), counts pairs whose cursor
 //        is ahead (`stalled`) and writes the block's number of entries;
 //   feed_scan_kernel      one block: the exclusive scan of the block sums and
@@ -16,19 +16,16 @@
 //        consecutive records) and stores the new cursors.
 // Order and cap come from the scan alone, so the same state and cursors give
 // the same bytes.
-#include "tick_common.hpp"
+#include "canon_view.hpp"
 
 namespace raftstep {
 
 namespace {
 
-constexpr int FEED_NO_SH = 2147483647;
-
 // The log-entry range of one group: per masked replica r the cursor c[r] as
 // read, lo[r] (the cursor moved past what left the ring) and n[r] entries
 // lo+1 .. lo+n to deliver; n = 0 and stalled for a pair whose cursor is ahead
-// of min(CommitIndex, LastApplied). The canonical view is derived exactly as
-// digest_kernel / store_range derive it.
+// of min(CommitIndex, LastApplied), all of the canonical view (canon_view.hpp).
 template <int R>
 struct FeedRange {
   int c[R], lo[R], n[R];
@@ -38,25 +35,16 @@ struct FeedRange {
 template <int R>
 __device__ __forceinline__ void feed_range(const DevPlanes& P, uint32_t g, int raft, uint32_t mask, uint32_t nm,
                                            const int32_t* cur, FeedRange<R>& f) {
-  const int meta = at(P.gmeta, g);
-  const int primary = meta & 0xF;
-  const bool msync = (meta & M_MSYNC) && primary < R;
-  const bool ssync = (meta & M_SSYNC) && primary < R;   // compressed state: the gss record
-  const SsRec ss = ssync ? P.gss[g] : SsRec{0, 0, 0, 0};
-  const LxRec lx = (ssync && uses_glx(meta)) ? P.glx[g] : LxRec{0, 0};
+  const CanonGroup<R> cg(P, g);
   f.stalled = 0;
   uint32_t k = 0;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     f.c[r] = f.lo[r] = f.n[r] = 0;
     if (!((mask >> r) & 1u)) continue;
-    // (the commit plane of an SSYNC group is read for SXS's stale leader only)
-    const bool plane = !ssync || (is_sxs(meta) && r == lx.dl);
-    const int pc = plane ? at(P.commit, rix<R>(g, r)) : 0;
-    const int l = ssync ? ss_last(ss, r, primary, meta, lx) : at(P.last, rix<R>(g, r));
-    const int cm = ssync ? ss_commit(ss, r, primary, meta, lx, pc) : pc;
-    // MSYNC: max(plane, LastApplied) (HWX), as the digest reads it
-    const int hwm = raft ? (msync ? max(at(P.hwm, rix<R>(g, r)), l) : at(P.hwm, rix<R>(g, r))) : l;
+    const int l = cg.last(P, r);
+    const int cm = cg.commit(P, r);
+    const int hwm = cg.hwm(P, r, raft, l);
     const int c = cur[size_t(g) * nm + k];
     ++k;
     const int hi = min(cm, l);
@@ -205,13 +193,13 @@ __global__ __launch_bounds__(256) void feed_emit_kernel(DevPlanes P, int raft, u
     s_lo[r][tid] = f.lo[r];
     s_n[r][tid] = f.n[r];
   }
-  if (n) {   // the ring phase segments and the shared form, as the digest reads them
-    const uint32_t rot = at(P.grot, g);
-    s_rot[tid] = rot | (uint32_t(at(P.grota, g)) << 16);
-    s_rotb[tid] = at(P.grotb, g);
-    s_sb[tid] = at(P.gsb, g);
-    s_sb2[tid] = at(P.gsb2, g);
-    s_shf[tid] = (P.sh && (rot & ROT_SH)) ? at(P.gshf, g) : FEED_NO_SH;
+  if (n) {   // the ring form (canon_view.hpp), staged for the lanes that fetch this group's entries
+    const RingForm rf = ring_form(P, g);
+    s_rot[tid] = rf.rot | (rf.rota << 16);
+    s_rotb[tid] = rf.rotb;
+    s_sb[tid] = rf.sb;
+    s_sb2[tid] = rf.sb2;
+    s_shf[tid] = rf.shf;
   }
   uint32_t inc = n;
 #pragma unroll
@@ -261,32 +249,17 @@ __global__ __launch_bounds__(256) void feed_emit_kernel(DevPlanes P, int raft, u
       const int idx = s_lo[r][t] + 1 + int(q);
       const uint32_t gs = blockIdx.x * 256u + t;
       const uint32_t rw = s_rot[t];
-      const uint32_t slot = ring_slot(idx, rw & 0xFFFFu, rw >> 16, s_rotb[t], s_sb[t], s_sb2[t], P.kmask);
-      int32_t lt;
-      int64_t lv;
-      uint32_t lc = 0;
-      if (idx >= s_shf[t]) {
-        const uint64_t shb = sh_tile(gs, P.KP);
-        const uint32_t so = sh_in_tile(gs, slot, P.sh_cs);
-        lt = at(P.sh_term + shb, so);
-        lv = at(P.sh_value + shb, so);
-        if (P.crc_on) lc = at(P.sh_crc + shb, so);
-      } else {
-        const uint64_t rb = ring_tile(gs, P.KP, R);
-        const uint32_t o = ring_in_tile(gs, R, slot, uint32_t(r));
-        lt = at(P.log_term + rb, o);
-        lv = at(P.log_value + rb, o);
-        if (P.crc_on) lc = at(P.log_crc + rb, o);
-      }
+      const RingForm rf{rw & 0xFFFFu, rw >> 16, s_rotb[t], s_sb[t], s_sb2[t], s_shf[t]};
+      const Entry e = canon_entry<R>(P, rf, gs, uint32_t(r), idx);
       const uint64_t gid = P.gbase + gs;
       w[0] = uint32_t(gid);
       w[1] = uint32_t(gid >> 32);
       w[2] = uint32_t(r);
       w[3] = uint32_t(idx);
-      w[4] = uint32_t(lt);
-      w[5] = lc;
-      w[6] = uint32_t(uint64_t(lv));
-      w[7] = uint32_t(uint64_t(lv) >> 32);
+      w[4] = uint32_t(e.term);
+      w[5] = e.crc;
+      w[6] = uint32_t(uint64_t(e.value));
+      w[7] = uint32_t(uint64_t(e.value) >> 32);
     }
     if (PAIRED) {
 #pragma unroll

@@ -15,13 +15,13 @@
 //        its hits by ballot and prefix inside the wave (consecutive hits are
 //        consecutive 16-B records) and the lane that writes the last record
 //        stores the id after it.
-// Gather: the canonical view of ids[0..n) into a staging buffer in the view's
-// layout, derived as digest_kernel derives it (gmeta, gss / glx or the planes,
-// max(hwm plane, last) under MSYNC, ring_slot over the three phase segments,
-// shared entries from the shared ring): one lane per listed group for the
-// scalars and the match / next rows, one wave per listed group for the logs.
+// Gather: the canonical view (canon_view.hpp) of ids[0..n), or of the range
+// [first, first + n), into a staging buffer in the view's layout: one lane per
+// listed group for the scalars and the match / next rows, one wave per listed
+// group for the logs. Every host read of the view goes through it
+// (raft_store_state / _range / _groups, raft_nodelog).
 // Restart: init_new_group (tick_common.hpp) for g = ids[i], feed cursors to 0.
-#include "tick_common.hpp"
+#include "canon_view.hpp"
 
 namespace raftstep {
 
@@ -88,60 +88,42 @@ __global__ __launch_bounds__(256) void group_emit_kernel(DevPlanes P, uint32_t s
   if (pos == cap - 1) *next = uint64_t(g) + 1u;
 }
 
-// The scalars and the match / next rows of listed group i < n, one lane each.
+// The scalars and the match / next rows of listed group i < n, one lane each
+// (ids null: the range g = first + i).
 template <int R>
-__global__ __launch_bounds__(256) void gather_scalar_kernel(DevPlanes P, int raft, const uint32_t* ids, uint32_t n,
-                                                            GatherOut o) {
+__global__ __launch_bounds__(256) void gather_scalar_kernel(DevPlanes P, int raft, uint32_t first, const uint32_t* ids,
+                                                            uint32_t n, GatherOut o) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
-  const uint32_t g = ids[i];
-  const int meta = at(P.gmeta, g);
-  const int primary = meta & 0xF, fault = (meta >> 4) & 7;
-  const bool msync = (meta & M_MSYNC) && primary < R;
-  const bool ssync = (meta & M_SSYNC) && primary < R;   // compressed state: the gss record
-  const SsRec ss = ssync ? P.gss[g] : SsRec{0, 0, 0, 0};
-  const LxRec lx = (ssync && uses_glx(meta)) ? P.glx[g] : LxRec{0, 0};
-  const int hb = (P.sh && (at(P.grot, g) & ROT_SH)) ? P.sh_hb : at(P.hb, g);   // (SH: implied)
+  const uint32_t g = ids ? ids[i] : first + i;
+  const CanonGroup<R> c(P, g);
+  const int hb = o.deadline ? c.hb(P) : 0;
   int last[R];
 #pragma unroll
-  for (int r = 0; r < R; ++r) last[r] = ssync ? ss_last(ss, r, primary, meta, lx) : at(P.last, rix<R>(g, r));
-  if (o.fault) o.fault[i] = uint8_t(fault);
+  for (int r = 0; r < R; ++r) last[r] = c.last(P, r);
+  if (o.fault) o.fault[i] = uint8_t(c.fault);
   if (o.iso_victim) o.iso_victim[i] = uint8_t(at(P.giso, g));
 #pragma unroll 1
   for (int r = 0; r < R; ++r) {
     const uint32_t x = at(P.rs, rix<R>(g, r));
-    const int role = int(x & 3u), dur = int(x >> 6);
+    const int role = rs_role(x), dur = rs_timeout(x);
     const int l = sel(last, r);
-    const int ts = at(P.tstart, rix<R>(g, r));
-    const uint32_t c = i * uint32_t(R) + uint32_t(r);
-    if (o.role) o.role[c] = uint8_t(role);
-    if (o.voted) o.voted[c] = uint8_t((x >> 2) & 15u);
-    if (o.term) o.term[c] = ssync ? ss_term(ss, r, meta, lx) : at(P.term, rix<R>(g, r));
-    if (o.last) o.last[c] = l;
-    if (o.commit) {
-      const int pc = at(P.commit, rix<R>(g, r));
-      o.commit[c] = ssync ? ss_commit(ss, r, primary, meta, lx, pc) : pc;
-    }
-    // deadline = effective timer start + d; followers / candidates also count the heartbeat
-    if (o.deadline) o.deadline[c] = (role == ROLE_L ? ts : max(ts, hb)) + dur;
-    if (o.timeout) o.timeout[c] = dur;
-    // MSYNC: max(plane, LastApplied) (HWX), as the digest reads it
-    if (o.hwm) o.hwm[c] = raft ? (msync ? max(at(P.hwm, rix<R>(g, r)), l) : at(P.hwm, rix<R>(g, r))) : l;
+    const uint32_t k = i * uint32_t(R) + uint32_t(r);
+    if (o.role) o.role[k] = uint8_t(role);
+    if (o.voted) o.voted[k] = uint8_t(rs_voted(x));
+    if (o.term) o.term[k] = c.term(P, r);
+    if (o.last) o.last[k] = l;
+    if (o.commit) o.commit[k] = c.commit(P, r);
+    if (o.deadline) o.deadline[k] = canon_deadline(role, at(P.tstart, rix<R>(g, r)), hb, dur);
+    if (o.timeout) o.timeout[k] = dur;
+    if (o.hwm) o.hwm[k] = c.hwm(P, r, raft, l);
     if (o.match || o.next) {
 #pragma unroll 1
       for (int p = 0; p < R; ++p) {
-        int m = 0, nx = 0;
-        if (role == ROLE_L && p != r) {
-          const int lp = sel(last, p);
-          const bool mp = msync && msync_peer(meta, lx, p);   // (SXS: the stale leader's row is explicit)
-          if (r == primary) m = mp ? lp : at(P.lmatch, rix<R>(g, p));
-          else m = at(prow(P.xmatch, r * R + p, P.Gp), g);
-          if (!raft) nx = m + 1;
-          else if (r == primary) nx = mp ? lp + 1 : at(P.lnext, rix<R>(g, p));
-          else nx = at(prow(P.xnext, r * R + p, P.Gp), g);
-        }
-        if (o.match) o.match[size_t(c) * R + p] = m;
-        if (o.next) o.next[size_t(c) * R + p] = nx;
+        int m, nx;
+        c.match_next(P, raft, role, r, p, last, &m, &nx);
+        if (o.match) o.match[size_t(k) * R + p] = m;
+        if (o.next) o.next[size_t(k) * R + p] = nx;
       }
     }
   }
@@ -152,52 +134,39 @@ __global__ __launch_bounds__(256) void gather_scalar_kernel(DevPlanes P, int raf
 // [(i R + r) K + s] contiguously; the reads are scattered over the group's
 // ring tile (its R-word runs, 64 R words apart). Slot s holds the largest
 // index idx <= last with (idx - 1) mod K == s, live when idx > max(0, hwm - K).
+// bad (may be null; with log_term only): the last-entry term check. Lane r < R
+// compares the term the engine caches for replica r's last entry with the
+// ring's entry at `last`; a mismatch records ~(g R + r) with atomicMax, so
+// the word, zero before the launch, stays zero when clean and otherwise names
+// the lowest (group, replica).
 template <int R>
-__global__ __launch_bounds__(256) void gather_log_kernel(DevPlanes P, int raft, const uint32_t* ids, uint32_t n,
-                                                         GatherOut o) {
+__global__ __launch_bounds__(256) void gather_log_kernel(DevPlanes P, int raft, uint32_t first, const uint32_t* ids,
+                                                         uint32_t n, GatherOut o, uint32_t* bad) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
   if (i >= n) return;   // (wave-uniform)
-  const uint32_t g = ids[i];
-  const int meta = at(P.gmeta, g);
-  const int primary = meta & 0xF;
-  const bool msync = (meta & M_MSYNC) && primary < R;
-  const bool ssync = (meta & M_SSYNC) && primary < R;
-  const SsRec ss = ssync ? P.gss[g] : SsRec{0, 0, 0, 0};
-  const LxRec lx = (ssync && uses_glx(meta)) ? P.glx[g] : LxRec{0, 0};
-  const uint32_t rot = at(P.grot, g), rota = at(P.grota, g), rotb = at(P.grotb, g);
-  const int sb = at(P.gsb, g), sb2 = at(P.gsb2, g);
-  // SH (ROT_SH): entries from shf on are read from the shared ring
-  const int shf = (P.sh && (rot & ROT_SH)) ? at(P.gshf, g) : 2147483647;
-  const uint64_t rb = ring_tile(g, P.KP, R), shb = sh_tile(g, P.KP);
+  const uint32_t g = ids ? ids[i] : first + i;
+  const CanonGroup<R> c(P, g);
+  const RingForm rf = ring_form(P, g);
+  // (a view without a field reads none of its ring words)
+  const int want = (o.log_term ? EW_TERM : 0) | (o.log_value ? EW_VALUE : 0) | (o.log_crc ? EW_CRC : 0);
+  if (bad && o.log_term && lane < uint32_t(R)) {
+    const int l = c.last(P, int(lane));
+    if (l > 0 && canon_entry<R>(P, rf, g, lane, l, EW_TERM).term != c.last_term(P, int(lane)))
+      atomicMax(bad, ~(g * uint32_t(R) + lane));
+  }
   const uint32_t K = P.K, RK = uint32_t(R) * K;
   const size_t ob = size_t(i) * RK;
   for (uint32_t j = lane; j < RK; j += 64u) {
     const uint32_t r = j / K, s = j & (K - 1u);
-    const int l = ssync ? ss_last(ss, int(r), primary, meta, lx) : at(P.last, rix<R>(g, int(r)));
-    const int hwm = raft ? (msync ? max(at(P.hwm, rix<R>(g, int(r))), l) : at(P.hwm, rix<R>(g, int(r)))) : l;
+    const int l = c.last(P, int(r));
+    const int hwm = c.hwm(P, int(r), raft, l);
     const int idx = l >= 1 ? l - int(uint32_t(l - 1 - int(s)) & (K - 1u)) : 0;
     const bool live = idx >= 1 && idx > hwm - int(K);
-    int32_t lt = 0;
-    int64_t lv = 0;
-    uint32_t lc = 0;
-    if (live) {
-      const uint32_t slot = ring_slot(idx, rot, rota, rotb, sb, sb2, P.kmask);
-      if (idx >= shf) {
-        const uint32_t so = sh_in_tile(g, slot, P.sh_cs);
-        if (o.log_term) lt = at(P.sh_term + shb, so);
-        if (o.log_value) lv = at(P.sh_value + shb, so);
-        if (o.log_crc && P.crc_on) lc = at(P.sh_crc + shb, so);
-      } else {
-        const uint32_t q = ring_in_tile(g, R, slot, r);
-        if (o.log_term) lt = at(P.log_term + rb, q);
-        if (o.log_value) lv = at(P.log_value + rb, q);
-        if (o.log_crc && P.crc_on) lc = at(P.log_crc + rb, q);
-      }
-    }
-    if (o.log_term) o.log_term[ob + j] = lt;
-    if (o.log_value) o.log_value[ob + j] = lv;
-    if (o.log_crc) o.log_crc[ob + j] = lc;
+    const Entry e = live ? canon_entry<R>(P, rf, g, r, idx, want) : Entry{0, 0, 0};
+    if (o.log_term) o.log_term[ob + j] = e.term;
+    if (o.log_value) o.log_value[ob + j] = e.value;
+    if (o.log_crc) o.log_crc[ob + j] = e.crc;
   }
 }
 
@@ -227,16 +196,17 @@ hipError_t launch_group_emit(int R, const DevPlanes& P, uint32_t select, uint32_
                                         static_cast<uint32_t*>(out), next));
   return hipGetLastError();
 }
-hipError_t launch_gather(int R, const DevPlanes& P, int raft, const uint32_t* ids, uint32_t n, const GatherOut& o,
-                         hipStream_t s) {
+hipError_t launch_gather(int R, const DevPlanes& P, int raft, uint32_t first, const uint32_t* ids, uint32_t n,
+                         const GatherOut& o, uint32_t* bad, hipStream_t s) {
   const bool scalars = o.role || o.voted || o.term || o.last || o.commit || o.deadline || o.timeout || o.match ||
                        o.fault || o.next || o.hwm || o.iso_victim;
   if (scalars) {
-    RAFT_DISPATCH_R(R, hipLaunchKernelGGL(gather_scalar_kernel<RR>, grid_for(n), dim3(256), 0, s, P, raft, ids, n, o));
+    RAFT_DISPATCH_R(R, hipLaunchKernelGGL(gather_scalar_kernel<RR>, grid_for(n), dim3(256), 0, s, P, raft, first, ids, n, o));
     if (hipError_t rc = hipGetLastError()) return rc;
   }
   if (o.log_term || o.log_value || o.log_crc) {   // (no log pointer: no ring word is read)
-    RAFT_DISPATCH_R(R, hipLaunchKernelGGL(gather_log_kernel<RR>, dim3((n + 3u) / 4u), dim3(256), 0, s, P, raft, ids, n, o));
+    RAFT_DISPATCH_R(R, hipLaunchKernelGGL(gather_log_kernel<RR>, dim3((n + 3u) / 4u), dim3(256), 0, s, P, raft, first, ids,
+                                          n, o, bad));
   }
   return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 // k_init.hip — NewNode / post-election initialisation kernels and the
 // semantics dispatch of the general and handler launchers.
-#include "tick_common.hpp"
+#include "canon_view.hpp"
 
 namespace raftstep {
 
@@ -50,8 +50,9 @@ __global__ __launch_bounds__(256) void init_steady_kernel(DevPlanes P, Trace T, 
 }
 
 // State digest (raft_state_digest): one lane per group derives the canonical
-// host view exactly as raft_store_state does (implicit MSYNC rows, heartbeat
-// timer starts, REF NextIndex = MatchIndex+1) and chains it through
+// host view (canon_view.hpp: implicit MSYNC rows, heartbeat timer starts, REF
+// NextIndex = MatchIndex+1; shared entries from the shared ring, the digest of
+// the materialised state without materialising it) and chains it through
 // splitmix64; the per-group digests are summed with one atomic per wave.
 // Same definition as oracle_state_digest().
 __device__ __forceinline__ uint64_t dg_mix(uint64_t h, uint64_t w) { return sm64(h ^ w); }
@@ -63,76 +64,39 @@ __global__ __launch_bounds__(256) void digest_kernel(DevPlanes P, int raft, uint
   const uint32_t g = blockIdx.x * 256u + threadIdx.x;
   uint64_t h = 0;
   if (g < P.G) {
-    const int meta = at(P.gmeta, g);
-    const int primary = meta & 0xF, fault = (meta >> 4) & 7;
-    const bool msync = (meta & M_MSYNC) && primary < R;
-    const bool ssync = (meta & M_SSYNC) && primary < R;   // compressed state: the gss record
-    const SsRec ss = ssync ? P.gss[g] : SsRec{0, 0, 0, 0};
-    const LxRec lx = (ssync && uses_glx(meta)) ? P.glx[g] : LxRec{0, 0};
-    const int hb = (P.sh && (at(P.grot, g) & ROT_SH)) ? P.sh_hb : at(P.hb, g);   // (SH: implied)
+    const CanonGroup<R> c(P, g);
+    const int hb = c.hb(P);
+    const RingForm rf = ring_form(P, g);
     int last[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) last[r] = ssync ? ss_last(ss, r, primary, meta, lx) : at(P.last, rix<R>(g, r));
+    for (int r = 0; r < R; ++r) last[r] = c.last(P, r);
     h = sm64(0x5241465444494721ULL ^ (P.gbase + g));
 #pragma unroll 1
     for (int r = 0; r < R; ++r) {
       const uint32_t x = at(P.rs, rix<R>(g, r));
-      const int role = int(x & 3u), dur = int(x >> 6);
+      const int role = rs_role(x), dur = rs_timeout(x);
       const int l = sel(last, r);
-      const int ts = at(P.tstart, rix<R>(g, r));
-      const int dl = (role == ROLE_L ? ts : max(ts, hb)) + dur;
-      // MSYNC: max(plane, LastApplied) (HWX; the plane is at most LastApplied without it)
-      const int hwm = raft ? (msync ? max(at(P.hwm, rix<R>(g, r)), l) : at(P.hwm, rix<R>(g, r))) : l;
-      h = dg_mix(h, uint64_t(role) | (uint64_t((x >> 2) & 15u) << 8) | (uint64_t(r) << 16));
-      const int tm = ssync ? ss_term(ss, r, meta, lx) : at(P.term, rix<R>(g, r));
-      const int cm = ssync ? ss_commit(ss, r, primary, meta, lx, at(P.commit, rix<R>(g, r))) : at(P.commit, rix<R>(g, r));
-      h = dg_mix(h, lo32(tm) | (lo32(l) << 32));
-      h = dg_mix(h, lo32(cm) | (lo32(dl) << 32));
+      const int dl = canon_deadline(role, at(P.tstart, rix<R>(g, r)), hb, dur);
+      const int hwm = c.hwm(P, r, raft, l);
+      h = dg_mix(h, uint64_t(role) | (uint64_t(rs_voted(x)) << 8) | (uint64_t(r) << 16));
+      h = dg_mix(h, lo32(c.term(P, r)) | (lo32(l) << 32));
+      h = dg_mix(h, lo32(c.commit(P, r)) | (lo32(dl) << 32));
       h = dg_mix(h, lo32(dur) | (lo32(hwm) << 32));
 #pragma unroll 1
       for (int p = 0; p < R; ++p) {
-        int m = 0, nx = 0;
-        if (role == ROLE_L && p != r) {
-          const int lp = sel(last, p);
-          const bool mp = msync && msync_peer(meta, lx, p);   // (SXS: the stale leader's row is explicit)
-          if (r == primary) m = mp ? lp : at(P.lmatch, rix<R>(g, p));
-          else m = at(prow(P.xmatch, r * R + p, P.Gp), g);
-          if (!raft) nx = m + 1;
-          else if (r == primary) nx = mp ? lp + 1 : at(P.lnext, rix<R>(g, p));
-          else nx = at(prow(P.xnext, r * R + p, P.Gp), g);
-        }
+        int m, nx;
+        c.match_next(P, raft, role, r, p, last, &m, &nx);
         h = dg_mix(h, lo32(m) | (lo32(nx) << 32));
       }
-      const uint64_t rb = ring_tile(g, P.KP, R);
-      const uint32_t rot = at(P.grot, g), rota = at(P.grota, g), rotb = at(P.grotb, g);
-      const int sb = at(P.gsb, g), sb2 = at(P.gsb2, g);
-      // SH (ROT_SH): entries from shf on are read from the shared ring (the
-      // digest of the materialised state, without materialising it)
-      const int shf = (P.sh && (rot & ROT_SH)) ? at(P.gshf, g) : 2147483647;
-      const uint64_t shb = sh_tile(g, P.KP);
 #pragma unroll 1
       for (int idx = hwm > int(P.K) ? hwm - int(P.K) + 1 : 1; idx <= l; ++idx) {
-        const uint32_t slot = ring_slot(idx, rot, rota, rotb, sb, sb2, P.kmask);
-        int32_t lt;
-        int64_t lv;
-        uint32_t lc = 0;
-        if (idx >= shf) {
-          const uint32_t so = sh_in_tile(g, slot, P.sh_cs);
-          lt = at(P.sh_term + shb, so);
-          lv = at(P.sh_value + shb, so);
-          if (P.crc_on) lc = at(P.sh_crc + shb, so);
-        } else {
-          const uint32_t o = ring_in_tile(g, R, slot, uint32_t(r));
-          lt = at(P.log_term + rb, o);
-          lv = at(P.log_value + rb, o);
-          if (P.crc_on) lc = at(P.log_crc + rb, o);
-        }
-        h = dg_mix(h, lo32(lt) | (lo32(idx) << 32));
-        h = dg_mix(h, uint64_t(lv));
-        h = dg_mix(h, P.crc_on ? uint64_t(lc) : 0ull);
+        const Entry e = canon_entry<R>(P, rf, g, uint32_t(r), idx);
+        h = dg_mix(h, lo32(e.term) | (lo32(idx) << 32));
+        h = dg_mix(h, uint64_t(e.value));
+        h = dg_mix(h, uint64_t(e.crc));   // (0 without payload_crc)
       }
     }
-    h = dg_mix(h, uint64_t(fault));
+    h = dg_mix(h, uint64_t(c.fault));
     const uint32_t gi = at(P.giso, g);
     if (gi) h = dg_mix(h, 0x1500u | gi);   // EXT leader-isolation victims (absent: digest unchanged)
     per_group[g] = h;

@@ -216,8 +216,12 @@ hipError_t launch_group_count(int R, const DevPlanes& P, uint32_t select, uint32
 hipError_t launch_group_emit(int R, const DevPlanes& P, uint32_t select, uint32_t first, const uint64_t* boff,
                              uint64_t cap, void* out, unsigned long long* next, hipStream_t s);
 // The canonical view (raft_state_view's fields and shapes, indexed by list
-// position) of groups ids[0..n) into device buffers; null fields are skipped,
-// and without a log field no ring word is read.
+// position; derived in canon_view.hpp) of groups ids[0..n), or with ids null
+// of the range [first, first + n), into device buffers; null fields are
+// skipped, and without a log field no ring word is read. bad (may be null): a
+// device word, zero before the launch, for the last-entry term check; nonzero
+// afterwards = ~(g R + r) of the lowest group and replica whose cached
+// last-entry term differs from the ring's (checked only with log_term).
 struct GatherOut {
   uint8_t *role, *voted;
   int32_t *term, *last, *commit, *deadline, *timeout, *match;
@@ -228,8 +232,8 @@ struct GatherOut {
   int32_t *next, *hwm;
   uint8_t* iso_victim;
 };
-hipError_t launch_gather(int R, const DevPlanes& P, int raft, const uint32_t* ids, uint32_t n, const GatherOut& o,
-                         hipStream_t s);
+hipError_t launch_gather(int R, const DevPlanes& P, int raft, uint32_t first, const uint32_t* ids, uint32_t n,
+                         const GatherOut& o, uint32_t* bad, hipStream_t s);
 // NewNode x R (init_new_group) for the distinct groups ids[0..n); cursors (may
 // be null): the open commit feed's, [G][nm], set to 0 for those groups.
 hipError_t launch_restart(int R, const DevPlanes& P, const Trace& T, const uint32_t* ids, uint32_t n, int32_t* cursors,

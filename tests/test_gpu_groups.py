@@ -133,6 +133,29 @@ def _check_store_groups(e, what, seed=5):
     return full
 
 
+# both sides of a 64-group ring tile and of a 256-group block, the ragged tail, the last group
+RANGES = ((0, 1), (63, 2), (255, 258), (1037, 64), (G - 1, 1))
+
+
+def _same_rows(got, want, rows, what):
+    for k in got:
+        w = want[k][rows]
+        assert got[k].dtype == w.dtype and got[k].shape == w.shape, (what, k)
+        if got[k].tobytes() != w.tobytes():
+            bad = np.argwhere(got[k] != w)
+            raise AssertionError(f"{what}: {k} differs from the oracle at {len(bad)} places, first (row, ...) "
+                                 f"{bad[0].tolist()}")
+
+
+def _check_ranges(e, so, what):
+    """store_state_range against the oracle's rows, with and without logs."""
+    for first, n in RANGES:
+        for logs in (True, False):
+            got = e.store_state_range(first, n, logs=logs)
+            assert set(got) == (set(so) if logs else set(so) - {"log_term", "log_value", "log_crc"})
+            _same_rows(got, so, slice(first, first + n), f"{what}: range ({first}, {n}) logs={logs}")
+
+
 def _run_steady(kw, e, o, calls=STEADY_CALLS):
     t = 1
     for k in calls:
@@ -158,7 +181,9 @@ def test_store_groups_equals_store_state_rows_steady_shared(kw):
     else:
         assert c["ticks_steady_form"] > 0 and c["ticks_list_skipped"] > 0
     full = _check_store_groups(e, "steady shared")
-    H.assert_same_state(full, o.store_state(), "steady shared vs the oracle")
+    so = o.store_state()
+    H.assert_same_state(full, so, "steady shared vs the oracle")
+    _check_ranges(e, so, "steady shared")
 
 
 def _forms(e, need, limit):
@@ -198,7 +223,11 @@ def test_store_groups_equals_store_state_rows_raft_leader_isolation_churn():
     seen = _forms(e, ("SSYNC", "LXS", "SXS", "HWX", "explicit"), G)
     print("forms at the read:", seen)
     assert all(seen.get(k, 0) > 0 for k in ("SSYNC", "LXS", "SXS", "HWX", "explicit")), seen
-    H.assert_same_state(full, o.store_state(), "C4 churn vs the oracle")
+    so = o.store_state()
+    H.assert_same_state(full, so, "C4 churn vs the oracle")
+    _check_ranges(e, so, "C4 churn")
+    for g in range(G):   # nodelog on every form
+        assert e.nodelog(g) == o.nodelog(g), f"nodelog of group {g}"
 
 
 def test_store_groups_equals_store_state_rows_ref_new_nodes_with_frozen_groups():
@@ -207,16 +236,20 @@ def test_store_groups_equals_store_state_rows_ref_new_nodes_with_frozen_groups()
     _tick(e, o, 0, 60)
     full = _check_store_groups(e, "REF new nodes at tick 60")
     assert (full["fault"] != 0).sum() >= 0.05 * G
-    H.assert_same_state(full, o.store_state(), "REF new nodes vs the oracle")
+    so = o.store_state()
+    H.assert_same_state(full, so, "REF new nodes vs the oracle")
+    _check_ranges(e, so, "REF new nodes")
 
 
 # 4 ------------------------------------------------------------------------
 @pytest.mark.parametrize("counters", [False, True], ids=["steady_form", "device_counters"])
 def test_looking_changes_nothing(counters):
-    """Two engines on case 3(a) run the same calls; one scans and stores 300
-    groups between them. counters: with the device lane counters on (the
-    shared-tick count; the steady form is then off by definition)."""
-    a, b = Engine(**STEADY_A), Engine(**STEADY_A)
+    """Two engines on case 3(a) run the same calls; one scans, stores 300
+    groups, takes the digest and reads node logs between them. counters: with
+    the device lane counters on (the shared-tick count; the steady form is then
+    off by definition). The oracle runs the same ticks: both engines end in its state."""
+    a, b, o = Engine(**STEADY_A), Engine(**STEADY_A), oracle.Oracle(**STEADY_A)
+    o.init_steady(-1, 0)
     ids = np.random.default_rng(3).permutation(G)[:300]
     for x in (a, b):
         x.init_steady(-1, 0)
@@ -227,17 +260,23 @@ def test_looking_changes_nothing(counters):
     for k in STEADY_CALLS:
         a.tick(t, k)
         b.tick(t, k)
+        o.tick(t, k, threads=THREADS)
         t += k
         hits, info = a.group_scan(FAULTED | LEADERLESS)
         assert info["matched"] == 0 and len(hits) == 0
-        a.store_groups(ids)
+        _same_rows(a.store_groups(ids), o.store_state(), ids, f"store_groups after tick {t - 1}")
+        assert np.array_equal(a.state_digest()[0], o.state_digest()[0])
+        for g in (0, 63, 64, 700, G - 1):
+            assert a.nodelog(g) == o.nodelog(g), f"nodelog of group {g} after tick {t - 1}"
     ca, cb = a.diag_read(), b.diag_read()
     print("looking:", {k: ca[k] for k in ("ticks", "ticks_steady_form", "ticks_list_skipped", "lean_sh")})
     for k in ("ticks", "ticks_steady_form", "ticks_list_skipped", "lean_sh"):
         assert ca[k] == cb[k], (k, ca[k], cb[k])
     assert ca["ticks_list_skipped"] > 0
     assert ca["lean_sh"] > 0 if counters else ca["ticks_steady_form"] > 0
-    assert np.array_equal(a.state_digest()[0], b.state_digest()[0])
+    want = o.state_digest()[0]
+    assert np.array_equal(a.state_digest()[0], want) and np.array_equal(b.state_digest()[0], want)
+    H.assert_same_state(a.store_state(), o.store_state(), "the looking engine vs the oracle")
 
 
 # 5 ------------------------------------------------------------------------
@@ -385,3 +424,21 @@ def test_a_poisoned_engine_answers_einternal():
         with pytest.raises(RaftError, match="engine state is invalid") as ei:
             call()
         assert ei.value.code == abi.RAFT_EINTERNAL
+
+
+# 9 ------------------------------------------------------------------------
+@pytest.mark.parametrize("payload_crc", [1, 0], ids=["crc", "nocrc"])
+def test_gather_chunk_edges(payload_crc):
+    """K = 4096: a group's view is 196,760 B with log_crc rows and 147,608 B
+    without, so a chunk of the gather is its 256-group floor either way and 600
+    groups go as 256 + 256 + 88; the range starts inside the full call's first
+    chunk and takes two of its own."""
+    kw = dict(replicas=3, groups=600, ring_depth=4096, entries_per_tick=1, client_period=1, payload_crc=payload_crc)
+    e, o = _pair(kw, "init_steady", -1, 0)
+    _tick(e, o, 1, 70)
+    so = o.store_state()
+    assert (so["last"] == 70).all() and (so["fault"] == 0).all()
+    H.assert_same_state(e.store_state(), so, "600 groups in three chunks vs the oracle")
+    _same_rows(e.store_state_range(250, 300), so, slice(250, 550), "range (250, 300)")
+    ids = np.random.default_rng(17).permutation(600)
+    _same_rows(e.store_groups(ids), so, ids, "store_groups of a permutation of every id")

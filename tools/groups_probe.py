@@ -8,6 +8,8 @@ tenth of its groups are frozen, then, as medians with the spread,
     (the only other way to see scattered groups),
   - raft_store_groups of 4096 random ids, alternating with
     raft_store_state_range(0, 4096) (the cheapest other way to that many groups),
+  - raft_state_digest with the per-group digests (the third reader of the
+    canonical view, csrc/canon_view.hpp),
   - raft_restart_groups of every hit and the first raft_tick call after it
     (repeats restart the same groups again: the same work).
 Every GPU step is a child process under its own time limit; one JSON line.
@@ -84,6 +86,7 @@ def child_store(groups, reps, full_stores):
     res = dict(groups=groups, ticks=t, matched=frozen, store_groups_hits_ms=[], store_state_ms=[],
                store_groups_4096_ms=[], store_state_range_4096_ms=[])
     e.store_groups(ids[:4096])   # (grows the staging buffer)
+    res["state_digest_ms"] = [timed(lambda: e.state_digest()) for _ in range(reps + 1)][1:]
     for i in range(reps):
         res["store_groups_hits_ms"].append(timed(lambda: e.store_groups(ids)))
         if i < full_stores:
@@ -149,7 +152,8 @@ def main():
     res.update(view_bytes_per_group=per, store_groups_hits_bytes=n * per, store_state_bytes=st["groups"] * per,
                store_groups_hits_ms=spread(st["store_groups_hits_ms"]), store_state_ms=spread(st["store_state_ms"]),
                store_groups_4096_ms=spread(st["store_groups_4096_ms"], 2),
-               store_state_range_4096_ms=spread(st["store_state_range_4096_ms"], 2))
+               store_state_range_4096_ms=spread(st["store_state_range_4096_ms"], 2),
+               state_digest_ms=spread(st["state_digest_ms"], 2))
     rs, _ = step(common + ["--child", "restart"])
     res.update(restart_ms=spread(rs["restart_ms"], 3), first_tick_after_ms=spread(rs["first_tick_after_ms"], 3),
                tick_before_ms=spread(rs["tick_before_ms"], 3), frozen_after_restarts=rs["frozen_after"])

@@ -48,6 +48,19 @@ enum raft_fault {
   RAFT_F_RING_EVICTED = 4,        /* EXT: entry older than the ring depth K was needed */
   RAFT_F_OVERFLOW = 5             /* EXT: a term/index would leave int32 (Go int is 64-bit) */
 };
+/* RAFT_F_OVERFLOW, the one value that does not fit. Terms and log indices
+ * reach 2^31-1; NextIndex = MatchIndex + 1 can be 2^31.
+ *   REF derives NextIndex at every use and compares it in 64 bits, as Go
+ *   does: a leader with MatchIndex 2^31-1 sends heartbeats with PrevLogIndex
+ *   2^31-1, no fault.
+ *   RAFT stores NextIndex as int32. An assignment that would store 2^31
+ *   freezes the group with RAFT_F_OVERFLOW at that assignment: winning an
+ *   election at LastApplied 2^31-1 (the votes stay granted, the candidate
+ *   stays a candidate, no row is written), and next = match + 1 after a
+ *   success at match 2^31-1 (the follower keeps what it appended, the
+ *   leader's rows and counters keep their values, later peers are not
+ *   reached). raft_load_state refuses (RAFT_EINVAL) a RAFT leader row whose
+ *   NextIndex is absent and whose MatchIndex is 2^31-1. */
 
 /* REF = main.go bit for bit (the drop-in). RAFT = EXT mode with the
  * Raft-paper rules (votedFor, up-to-date check, truncate-on-conflict,
@@ -156,7 +169,9 @@ typedef struct raft_state_view {
   int64_t* log_value; /* Log.Value (main.go:48) */
   uint32_t* log_crc;  /* EXT: CRC32C of each ring entry (0 when payload_crc is off) */
   int32_t* next;      /* Node.NextIndex [(g*R + leader)*R + peer] (REF: match+1); 0 for non-leaders.
-                         Optional on load: absent or 0 derives match+1 (REF ignores it) */
+                         Optional on load: absent or 0 derives match+1 (REF ignores it).
+                         REF with match == 2^31-1: the derived value is 2^31, and the view and the
+                         digest carry its low 32 bits (INT32_MIN); see RAFT_F_OVERFLOW */
   int32_t* hwm;       /* [g*R + r] highest LastApplied ever (== last in REF); the ring holds (hwm-K, last].
                          Optional on load: absent or < last means last (REF ignores it) */
   uint8_t* iso_victim;/* per group, EXT leader-isolation mode: victims of the windows in flight, one nibble

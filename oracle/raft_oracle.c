@@ -114,8 +114,13 @@ typedef struct {                                 /* Node (main.go:14-39) */
   int64_t match[RAFT_MAX_REPLICAS];              /* MatchIndex; REF: NextIndex = match+1 */
   int64_t next[RAFT_MAX_REPLICAS];               /* NextIndex (RAFT mode only; REF derives it) */
   int64_t hwm;                                   /* highest LastApplied ever (ring window; == last in REF) */
-  o_ent* log;
+  o_ent* log;                                    /* log[k] is entry base + k + 1 */
   int64_t cap;
+  /* Leading entries that are not materialised. 0 for a log grown from empty;
+   * oracle_load_state sets max(0, hwm - K), the entries that the ring-depth
+   * rule (get_log_term) lets nobody read, so a log near index 2^31 costs K
+   * entries. Never above last: truncation stops above hwm - K. */
+  int64_t base;
 } o_node;
 
 typedef struct {
@@ -172,8 +177,9 @@ typedef struct {                                 /* one handler invocation's con
 
 typedef struct {                                 /* AppendEntriesRequest (main.go:289-296) */
   int64_t term, prev_idx, prev_term, lc;
-  const o_ent* ents;
+  const o_ent* ents;                             /* Logs[virt..n) */
   int64_t n;
+  int64_t virt;                                  /* leading entries of Logs the sender does not hold (REF whole log) */
   int corrupt;                                   /* EXT: last entry arrives with a flipped bit */
 } o_ae;
 typedef struct { int64_t term, match; int ok; } o_aer;  /* AppendEntriesResponse (main.go:298-302) */
@@ -185,15 +191,30 @@ static void set_fault(o_group* G, int f) {
 /* append(n.Log, ...) (main.go:148, 328): Go slices grow by doubling. */
 static void log_append(o_node* n, const o_ent* src, int64_t cnt) {
   if (cnt <= 0) return;
-  if (n->last + cnt > n->cap) {
+  const int64_t held = n->last - n->base;
+  if (held + cnt > n->cap) {
     int64_t nc = n->cap ? n->cap : 8;
-    while (nc < n->last + cnt) nc *= 2;
+    while (nc < held + cnt) nc *= 2;
     n->log = (o_ent*)realloc(n->log, (size_t)nc * sizeof(o_ent));
     n->cap = nc;
   }
-  memmove(n->log + n->last, src, (size_t)cnt * sizeof(o_ent));
+  memmove(n->log + held, src, (size_t)cnt * sizeof(o_ent));
   n->last += cnt;
   if (n->last > n->hwm) n->hwm = n->last;
+}
+/* Entry i of the log, base < i <= last. */
+static const o_ent* ent_at(const o_node* n, int64_t i) { return &n->log[i - 1 - n->base]; }
+/* Append Logs[0..cnt) whose first `virt` entries the sender does not hold
+ * (the REF whole-log send of a leader loaded with a window): the receiver
+ * keeps what the sender held, as the engine's ring keeps the last K, and its
+ * own older entries drop out of the window with the virtual ones. */
+static void log_append_from(o_node* n, const o_ent* src, int64_t cnt, int64_t virt) {
+  if (virt > 0) {
+    n->last += virt;
+    n->base = n->last;
+    if (n->last > n->hwm) n->hwm = n->last;
+  }
+  log_append(n, src, cnt - virt);
 }
 
 /* GetLog(i) = Log[i-1] (main.go:403-405): panics outside [1, len]; the
@@ -202,7 +223,7 @@ static void log_append(o_node* n, const o_ent* src, int64_t cnt) {
 static int get_log_term(const o_ctx* c, o_group* G, const o_node* n, int64_t i, int64_t* out) {
   if (i < 1 || i > n->last) { set_fault(G, RAFT_F_PANIC_GETLOG); return 0; }
   if (i <= n->hwm - (int64_t)c->cfg->ring_depth) { set_fault(G, RAFT_F_RING_EVICTED); return 0; }
-  *out = n->log[i - 1].term;
+  *out = ent_at(n, i)->term;
   return 1;
 }
 
@@ -235,12 +256,13 @@ static o_aer follower_ae(const o_ctx* c, o_group* G, int x, const o_ae* r) {
   if (n->last + r->n > I32MAX) { set_fault(G, RAFT_F_OVERFLOW); return res; }
   if (c->cfg->payload_crc) {                             /* EXT: verify what will be stored (last K) */
     int64_t j0 = r->n > (int64_t)c->cfg->ring_depth ? r->n - (int64_t)c->cfg->ring_depth : 0;
-    for (int64_t j = j0; j < r->n; ++j) {
-      int64_t v = r->ents[j].value ^ ((r->corrupt && j == r->n - 1) ? 1 : 0);
-      if (oracle_entry_crc(r->ents[j].term, v) != r->ents[j].crc) return res;
+    for (int64_t j = j0; j < r->n; ++j) {               /* j0 >= virt: a window holds the last K */
+      const o_ent* e = &r->ents[j - r->virt];
+      int64_t v = e->value ^ ((r->corrupt && j == r->n - 1) ? 1 : 0);
+      if (oracle_entry_crc(e->term, v) != e->crc) return res;
     }
   }
-  log_append(n, r->ents, r->n);                          /* 148-149 */
+  log_append_from(n, r->ents, r->n, r->virt);            /* 148-149 */
   if (r->lc > n->commit)                                 /* 151-152: min(LC, len(Log)+1) */
     n->commit = r->lc < n->last + 1 ? r->lc : n->last + 1;
   n->term = r->term;                                     /* 155 */
@@ -363,18 +385,18 @@ static void leader_round(o_ctx* c, o_group* G, int L) {
     if (p == L) continue;
     if (dropped(c, L, p)) { c->st[RAFT_STAT_AE_FAIL]++; continue; }  /* EXT */
     o_ae r;
-    r.term = n->term; r.lc = n->commit;
+    r.term = n->term; r.lc = n->commit; r.virt = 0;
     r.corrupt = oracle_corrupted(c->cfg, c->gid, (uint32_t)p, c->tick);
     int64_t nxt = n->match[p] + 1;                       /* NextIndex == MatchIndex + 1 */
     if (nxt <= n->last) {                                /* 341 */
       if (nxt == 1) {                                    /* 343-351: whole log, PrevLogIndex 0 */
-        r.ents = n->log; r.n = n->last;
+        r.ents = n->log; r.n = n->last; r.virt = n->base;
         r.prev_term = n->term; r.prev_idx = 0;
       } else {                                           /* 353-360 */
         if (nxt < 1) { set_fault(G, RAFT_F_PANIC_GETLOG); return; }  /* GetLogsFrom(<1) panics */
         int64_t pt;
         if (!get_log_term(c, G, n, n->match[p], &pt)) return;       /* GetLog(MatchIndex) */
-        r.ents = n->log + (nxt - 1); r.n = n->last - nxt + 1;
+        r.ents = ent_at(n, nxt); r.n = n->last - nxt + 1;
         r.prev_term = pt; r.prev_idx = n->match[p];
       }
     } else {                                             /* 364-371: heartbeat, PrevLogTerm = Term */
@@ -422,7 +444,7 @@ static void client_append(const o_ctx* c, o_group* G, int L, int64_t value) {
  * (382-391); commit = min(LC, last new entry) (152); any higher term steps
  * down (265-268, 373-378). voted holds votedFor (-1 = none).
  * ==================================================================== */
-static int64_t last_term_of(const o_node* n) { return n->last ? n->log[n->last - 1].term : 0; }
+static int64_t last_term_of(const o_node* n) { return n->last ? ent_at(n, n->last)->term : 0; }
 
 /* Figure 2, all servers: a higher term in any RPC -> adopt it, forget the
  * vote, and (if not already) become a follower. */
@@ -517,6 +539,9 @@ static int r_candidate_round(o_ctx* c, o_group* G, int cand) {
     if (grant) { count++; c->st[RAFT_STAT_VOTES_GRANTED]++; }
   }
   if (n->role == RAFT_CANDIDATE && 2 * count > R) {
+    /* EXT: NextIndex = last + 1 would be 2^31 (RAFT_F_OVERFLOW, raftstep.h): the
+     * election is won but the candidate's role and rows stay as they are */
+    if (n->last >= I32MAX) { set_fault(G, RAFT_F_OVERFLOW); return 0; }
     n->role = RAFT_LEADER;
     for (int p = 0; p < R; ++p) { n->match[p] = 0; n->next[p] = n->last + 1; }
     c->st[RAFT_STAT_ELECTIONS_WON]++;
@@ -553,7 +578,7 @@ static void r_leader_round(o_ctx* c, o_group* G, int L) {
     if (n->role != RAFT_LEADER) return;
     if (dropped(c, L, p)) { c->st[RAFT_STAT_AE_FAIL]++; continue; }
     o_ae r;
-    r.term = n->term; r.lc = n->commit;
+    r.term = n->term; r.lc = n->commit; r.virt = 0;
     r.corrupt = oracle_corrupted(c->cfg, c->gid, (uint32_t)p, c->tick);
     int64_t nxt = n->next[p];
     if (nxt < 1 || nxt > n->last + 1) { set_fault(G, RAFT_F_PANIC_GETLOG); return; }
@@ -561,12 +586,15 @@ static void r_leader_round(o_ctx* c, o_group* G, int L) {
     r.prev_idx = nxt - 1;
     r.prev_term = 0;
     if (r.prev_idx > 0 && !get_log_term(c, G, n, r.prev_idx, &r.prev_term)) return;
-    r.ents = n->log + (nxt - 1);
+    r.ents = n->last >= nxt ? ent_at(n, nxt) : NULL;
     r.n = n->last - nxt + 1;
     o_aer res = r_deliver_ae(c, G, p, &r);
     if (G->fault) return;
     if (res.term > n->term) { r_observe_term(c, G, L, res.term); c->st[RAFT_STAT_AE_FAIL]++; return; }
     if (res.ok) {
+      /* EXT: NextIndex = match + 1 would be 2^31: the follower has answered,
+       * the leader's rows and counters keep their values */
+      if (res.match >= I32MAX) { set_fault(G, RAFT_F_OVERFLOW); return; }
       n->match[p] = res.match;
       n->next[p] = res.match + 1;
       c->st[RAFT_STAT_AE_OK]++;
@@ -646,7 +674,7 @@ static void free_logs(oracle* o) {
   for (uint64_t g = 0; g < o->cfg.groups; ++g)
     for (uint32_t r = 0; r < o->cfg.replicas; ++r) {
       free(o->g[g].n[r].log);
-      o->g[g].n[r].log = NULL; o->g[g].n[r].cap = 0;
+      o->g[g].n[r].log = NULL; o->g[g].n[r].cap = 0; o->g[g].n[r].base = 0;
     }
 }
 
@@ -735,25 +763,31 @@ int oracle_load_state(oracle* o, const raft_state_view* v) {
         /* RAFT: a zero (or absent) NextIndex derives match+1, as REF always does */
         int32_t nx = (o->cfg.semantics == RAFT_SEM_RAFT && v->next) ? v->next[i * R + p] : 0;
         n->next[p] = nx > 0 ? nx : n->match[p] + 1;
+        /* RAFT stores NextIndex, and 2^31 is not one (RAFT_F_OVERFLOW, raftstep.h) */
+        if (o->cfg.semantics == RAFT_SEM_RAFT && n->role == RAFT_LEADER && p != r && n->next[p] > I32MAX)
+          return RAFT_EINVAL;
       }
       int64_t last = v->last[i];
       if (last < 0) return RAFT_EINVAL;
       /* hwm below last (e.g. an all-zero plane) means "= last"; REF never truncates so hwm == last */
       int64_t hwm = (o->cfg.semantics == RAFT_SEM_RAFT && v->hwm && v->hwm[i] > last) ? v->hwm[i] : last;
       if (last > 0 && last <= hwm - (int64_t)K) return RAFT_EINVAL;   /* last entry outside the ring window */
-      n->last = 0;
-      if (last > 0) {
-        o_ent* tmp = (o_ent*)calloc((size_t)last, sizeof(o_ent));
-        for (int64_t idx = hwm > K ? hwm - K + 1 : 1; idx <= last; ++idx) {
+      /* only the window that get_log_term lets anyone read is materialised */
+      n->base = n->last = (last > 0 && hwm > K) ? hwm - K : 0;   /* (an empty log grows dense) */
+      if (last > n->base) {
+        const int64_t b = n->base;
+        o_ent* tmp = (o_ent*)calloc((size_t)(last - b), sizeof(o_ent));
+        for (int64_t idx = b + 1; idx <= last; ++idx) {
           uint64_t s = i * K + (uint64_t)((idx - 1) & (K - 1));
-          tmp[idx - 1].term = v->log_term[s];
-          tmp[idx - 1].value = v->log_value[s];
-          tmp[idx - 1].crc = v->log_crc ? v->log_crc[s]
-                           : (o->cfg.payload_crc ? oracle_entry_crc(v->log_term[s], v->log_value[s]) : 0u);
+          tmp[idx - 1 - b].term = v->log_term[s];
+          tmp[idx - 1 - b].value = v->log_value[s];
+          tmp[idx - 1 - b].crc = v->log_crc ? v->log_crc[s]
+                               : (o->cfg.payload_crc ? oracle_entry_crc(v->log_term[s], v->log_value[s]) : 0u);
         }
-        log_append(n, tmp, last);
+        log_append(n, tmp, last - b);
         free(tmp);
       }
+      n->last = last;
       n->hwm = hwm;
     }
   }
@@ -793,9 +827,9 @@ void oracle_store_state(const oracle* o, raft_state_view* v) {
       int64_t lo = n->hwm > K ? n->hwm - K + 1 : 1;
       for (int64_t idx = lo; idx <= n->last; ++idx) {
         uint64_t s = i * K + (uint64_t)((idx - 1) & (K - 1));
-        if (v->log_term) v->log_term[s] = (int32_t)n->log[idx - 1].term;
-        if (v->log_value) v->log_value[s] = n->log[idx - 1].value;
-        if (v->log_crc) v->log_crc[s] = n->log[idx - 1].crc;
+        if (v->log_term) v->log_term[s] = (int32_t)ent_at(n, idx)->term;
+        if (v->log_value) v->log_value[s] = ent_at(n, idx)->value;
+        if (v->log_crc) v->log_crc[s] = ent_at(n, idx)->crc;
       }
     }
   }
@@ -903,7 +937,7 @@ int oracle_append_entries(oracle* o, int64_t now_tick, const raft_ae_req* reqs, 
     }
     o_ae r;
     r.term = q->term; r.prev_idx = q->prev_log_index; r.prev_term = q->prev_log_term;
-    r.lc = q->leader_commit; r.n = (int64_t)q->n_entries;
+    r.lc = q->leader_commit; r.n = (int64_t)q->n_entries; r.virt = 0;
     r.ents = ents;
     r.corrupt = 0;
     o_aer a = is_raft(&c) ? r_deliver_ae(&c, G, (int)q->to, &r) : deliver_ae(&c, G, (int)q->to, &r);
@@ -1032,9 +1066,9 @@ void oracle_state_digest(const oracle* o, uint64_t* per_group, uint64_t* total) 
         h = dg_mix(h, lo32(m) | (lo32(nx) << 32));
       }
       for (int64_t idx = n->hwm > K ? n->hwm - K + 1 : 1; idx <= n->last; ++idx) {
-        h = dg_mix(h, lo32(n->log[idx - 1].term) | (lo32(idx) << 32));
-        h = dg_mix(h, (uint64_t)n->log[idx - 1].value);
-        h = dg_mix(h, (uint64_t)n->log[idx - 1].crc);
+        h = dg_mix(h, lo32(ent_at(n, idx)->term) | (lo32(idx) << 32));
+        h = dg_mix(h, (uint64_t)ent_at(n, idx)->value);
+        h = dg_mix(h, (uint64_t)ent_at(n, idx)->crc);
       }
     }
     h = dg_mix(h, (uint64_t)G->fault);

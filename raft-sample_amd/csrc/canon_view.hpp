@@ -85,10 +85,10 @@ __device__ __forceinline__ int canon_deadline(int role, int tstart, int hb, int 
 
 // Where a group's entries are: the three ring phase segments (ring_slot) and,
 // in shared form (SH), the first index that lives in the shared ring.
-constexpr int CANON_NO_SH = 2147483647;
 struct RingForm {
   uint32_t rot, rota, rotb;
   int sb, sb2, shf;
+  bool sh;   // shared form; a flag, not a sentinel in shf: 2^31-1 is a log index
 };
 __device__ __forceinline__ RingForm ring_form(const DevPlanes& P, uint32_t g) {
   RingForm f;
@@ -97,7 +97,8 @@ __device__ __forceinline__ RingForm ring_form(const DevPlanes& P, uint32_t g) {
   f.rotb = at(P.grotb, g);
   f.sb = at(P.gsb, g);
   f.sb2 = at(P.gsb2, g);
-  f.shf = (P.sh && (f.rot & ROT_SH)) ? at(P.gshf, g) : CANON_NO_SH;
+  f.sh = P.sh && (f.rot & ROT_SH);
+  f.shf = f.sh ? at(P.gshf, g) : 0;
   return f;
 }
 // Entry idx of replica r's log, from the shared ring for idx >= shf and the
@@ -114,7 +115,7 @@ __device__ __forceinline__ Entry canon_entry(const DevPlanes& P, const RingForm&
                                              int want = EW_ALL) {
   Entry e{0, 0, 0};
   const uint32_t slot = ring_slot(idx, f.rot, f.rota, f.rotb, f.sb, f.sb2, P.kmask);
-  if (idx >= f.shf) {
+  if (f.sh && idx >= f.shf) {
     const uint64_t shb = sh_tile(g, P.KP);
     const uint32_t so = sh_in_tile(g, slot, P.sh_cs);
     if (want & EW_TERM) e.term = at(P.sh_term + shb, so);

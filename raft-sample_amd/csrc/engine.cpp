@@ -1108,7 +1108,13 @@ int raft_load_state(raft_engine* e, const raft_state_view* v) {
           if (p == r) continue;
           const int32_t m = v->match[c * R + p];
           // RAFT: NextIndex as given, 0/absent derives match+1 (the oracle's rule)
-          const int32_t nx = (v->next && v->next[c * R + p] > 0) ? v->next[c * R + p] : m + 1;
+          // (REF derives it at every use, in 64 bits, so MatchIndex 2^31-1 loads; RAFT stores
+          // it, and 2^31 is not a NextIndex: see RAFT_F_OVERFLOW)
+          const int64_t nx64 = (v->next && v->next[c * R + p] > 0) ? int64_t(v->next[c * R + p]) : int64_t(m) + 1;
+          if (raft && nx64 > 2147483647)
+            return fail(RAFT_EINVAL, "group %llu replica %llu: NextIndex of MatchIndex 2^31-1 does not fit",
+                        (unsigned long long)g, (unsigned long long)r);
+          const int32_t nx = raft ? int32_t(nx64) : 0;
           if (int(r) == primary) {
             lm[g * R + p] = m;
             if (raft) ln[g * R + p] = nx;

@@ -5,6 +5,13 @@
 
 namespace raftstep {
 
+// The highest LastApplied a fast path may leave behind. REF: the int32 ceiling.
+// RAFT keeps NextIndex = LastApplied + 1 in an int32 plane (or implies it), and
+// 2^31 is not a NextIndex (RAFT_F_OVERFLOW, raftstep.h): a tick that would end at
+// 2^31-1 goes to the general path, which raises the fault where the rule puts it.
+template <bool RAFT>
+constexpr int64_t IDX_TOP = RAFT ? int64_t(I32MAX) - 1 : int64_t(I32MAX);
+
 // Diagnostics build only (make DIAG=1 / -DRAFTSTEP_WAVE_PROF): lane 0 of
 // every list-kernel wave adds the cycles (s_memtime) it spent in each phase
 // to the device counters (P.dbg, raft_diag_read) instead of the class
@@ -513,7 +520,7 @@ __device__ __forceinline__ bool fast_group(const DevPlanes& P, const Trace& T, u
     if (go && !bail && lx) {
       // (a truncated log, high-water mark above its length, would break MSYNC's hwm == last)
       // (fresh rows are in step only for a follower that accepts this tick; here nobody does)
-      bail = int64_t(Ll) + n > I32MAX || n >= int(P.K) || Ll == 0 || hwup != 0u || fresh != 0u;
+      bail = int64_t(Ll) + n > IDX_TOP<RAFT> || n >= int(P.K) || Ll == 0 || hwup != 0u || fresh != 0u;
 #pragma unroll
       for (int p = 0; p < R; ++p) bail |= p != c && m[p] != last[p];
       int ts[R], rsv[R];
@@ -644,7 +651,7 @@ __device__ __forceinline__ bool fast_group(const DevPlanes& P, const Trace& T, u
       }
     }
     const bool gom = go && !lx;   // the main steady-state path
-    if (gom && !bail) bail = int64_t(Ll) + n > I32MAX || n >= int(P.K);
+    if (gom && !bail) bail = int64_t(Ll) + n > IDX_TOP<RAFT> || n >= int(P.K);
     // REF with payload CRC (round 6): one follower whose last AppendEntries
     // was rejected (a corrupted copy, EXT) lags — its log ends at its
     // MatchIndex m < Ll (REF keeps MatchIndex on a failure, main.go:375-378).
@@ -670,7 +677,7 @@ __device__ __forceinline__ bool fast_group(const DevPlanes& P, const Trace& T, u
         }
         if (!RAFT && CRC && p != c && n > 0 && m[p] > 0 && m[p] < Ll && m[p] == last[p] &&
             Ll + n - m[p] < int(P.K)) {
-          const bool nocopy = shf >= 0 && m[p] + 1 >= shf;
+          const bool nocopy = shf >= 0 && int64_t(m[p]) + 1 >= shf;
           if (nocopy || lg < 0) {
             lgm |= 1u << p;
             if (!nocopy) lg = p;
@@ -694,7 +701,7 @@ __device__ __forceinline__ bool fast_group(const DevPlanes& P, const Trace& T, u
         if (role != ((meta & M_STEADY) ? ROLE_F : stale ? ROLE_L : ROLE_C)) bail = true;
         // (the stale leader appends at its own log's end with the ring rotation as it stands:
         // an empty group would pick a new phase, see below)
-        if (stale && (x_term >= Lt || int64_t(sel(last, xi)) + n > I32MAX || empty)) bail = true;
+        if (stale && (x_term >= Lt || int64_t(sel(last, xi)) + n > IDX_TOP<RAFT> || empty)) bail = true;
         const int dl = max(RW.at(PL_TSTART, xi), GW.hb()) + (x_rs >> 6);
         if (!stale && dl <= T.now) {   // timer.C: Term++, vote for itself, new candidate timer (Raft §5.2)
           if (x_term >= I32MAX) bail = true;
@@ -759,7 +766,7 @@ __device__ __forceinline__ bool fast_group(const DevPlanes& P, const Trace& T, u
             else if (pi < 1 || pi > l || pi <= l - int(P.K) || pi != l) bail = true;
             else ok = lt[p] == pt;                                // 142-145 (GetLog(l) == last entry)
           }
-          if (ok && int64_t(l) + np > I32MAX) bail = true;
+          if (ok && int64_t(l) + np > IDX_TOP<RAFT>) bail = true;
           if (ok && ((crcbad >> p) & 1u)) ok = false;             // EXT: payload rejected
         }
         if (ok) {
@@ -768,8 +775,9 @@ __device__ __forceinline__ bool fast_group(const DevPlanes& P, const Trace& T, u
           if (n && lt[p] != Lt) ltch |= 1u << p;
           if (Lc > commit[p]) {                                   // 151-152
             // REF: min(LC, len(Log)+1); RAFT: min(leaderCommit, index of last new entry)
-            const int cap = RAFT ? nl : nl + 1;
-            const int nc = Lc < cap ? Lc : cap;
+            // (len+1 in 64 bits: it is 2^31 at nl == 2^31-1, and LC stays below it)
+            const int64_t cap = RAFT ? int64_t(nl) : int64_t(nl) + 1;
+            const int nc = int64_t(Lc) < cap ? Lc : int(cap);
             if (nc != commit[p]) { commit[p] = nc; cch |= 1u << p; }
           }
           if (nl != m[p]) { m[p] = nl; mch |= 1u << p; }          // 156 -> 375-377
@@ -812,7 +820,7 @@ __device__ __forceinline__ bool fast_group(const DevPlanes& P, const Trace& T, u
       sr_hw = max(hws, ls + n);   // its high-water mark after its own client append
       const int Kd = int(P.K);
       // (n == 0 would leave sr's LastApplied out of the row stores below: general path)
-      bail |= n == 0 || sel(term, sr) >= Lt || L0 < 0 || L0 > ls || L0 > Ll || int64_t(ls) + n > I32MAX ||
+      bail |= n == 0 || sel(term, sr) >= Lt || L0 < 0 || L0 > ls || L0 > Ll || int64_t(ls) + n > IDX_TOP<RAFT> ||
               hwc < Ll || (L0 >= 1 ? L0 : 1) <= max(hwc, Ll + n) - Kd ||   // NextIndex / prevLogTerm in the ring
               (L0 >= 1 ? L0 : 1) <= sr_hw - Kd;   // sr's entries L0 (prevLogTerm) and L0+1 (conflict) are read
       // every read this needs is issued at once (one round trip for the lane,
@@ -1957,7 +1965,7 @@ __device__ __forceinline__ void lean_tick(const DevPlanes& P, const Trace& T, un
         // phase. Commit (r_leader_commit): the majority order statistic is the
         // followers' length L, an entry of the current term (SSYNC).
         const int Lc = L + gx.k;
-        take = gx.dl > T.now && n < int(P.K) && int64_t(Lc) + n <= I32MAX && (n == 0 || ((Lc + rot) & int(P.kmask)) == ph);
+        take = gx.dl > T.now && n < int(P.K) && int64_t(Lc) + n <= IDX_TOP<RAFT> && (n == 0 || ((Lc + rot) & int(P.kmask)) == ph);
         cl2 = L > s.cl ? L : s.cl;
         // The whole row, not only the leader's column, when every
         // follower's slot there is dead: with KP = 2K slots, all of a
@@ -1987,7 +1995,7 @@ __device__ __forceinline__ void lean_tick(const DevPlanes& P, const Trace& T, un
         // (index L+k+1+e, current segment: k >= 0) go in its column, inside
         // the common row when xs is in the global phase, else at its own slots.
         const int xs = gx.dl, k = gx.k;
-        take = L > 0 && k >= 0 && int64_t(L) + k + n <= I32MAX && n < int(P.K) && s.cl <= L + n && !(meta & M_HWX);
+        take = L > 0 && k >= 0 && int64_t(L) + k + n <= IDX_TOP<RAFT> && n < int(P.K) && s.cl <= L + n && !(meta & M_HWX);
         nl = L + n;
         cl2 = nl > s.cl ? nl : s.cl;
         cf2 = s.cl > s.cf ? s.cl : s.cf;
@@ -2006,7 +2014,7 @@ __device__ __forceinline__ void lean_tick(const DevPlanes& P, const Trace& T, un
         // (the followers' CommitIndex min(LeaderCommit, last new entry) is the
         // leader's only while that is at most L+n: a leader's CommitIndex above
         // its log, left by a truncation, goes to the list kernel)
-        take &= L > 0 && int64_t(L) + n <= I32MAX && n < int(P.K) && s.cl <= L + n;
+        take &= L > 0 && int64_t(L) + n <= IDX_TOP<RAFT> && n < int(P.K) && s.cl <= L + n;
         if (RAFT && take && (meta & M_HWX)) {
           // every AppendEntries' prevLogIndex (L) and NextIndex (L+1) must stay
           // inside the ring window of every log: max hwm < L+K (r_deliver_ae /
@@ -2367,7 +2375,7 @@ __global__ __launch_bounds__(256) void tick_fused_kernel(DevPlanes P, Trace T, i
     const int n = int(Tj.client_entries());
     const int ph = int(Tj.entries_before(Tj.tick) & P.kmask);
     // the lean kernel's normal class, in phase (init_steady puts every group there)
-    bool take = live && L > 0 && int64_t(L) + n <= I32MAX && n < int(P.K) && cl <= L + n &&
+    bool take = live && L > 0 && int64_t(L) + n <= IDX_TOP<RAFT> && n < int(P.K) && cl <= L + n &&
                 (n == 0 || ((L + rot) & int(P.kmask)) == ph);
     if (live && !take) { pass = true; live = false; }
     int committed = 0;

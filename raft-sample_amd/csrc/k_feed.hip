@@ -75,7 +75,8 @@ __global__ __launch_bounds__(256) void feed_count_kernel(DevPlanes P, int raft, 
                                                          uint32_t* bsum, unsigned long long* tot, int mode) {
   __shared__ uint32_t s_w[4];
   const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-  uint32_t n = 0, lost = 0, stalled = 0;
+  uint32_t n = 0, stalled = 0;
+  unsigned long long lost = 0;   // (R cursors may each be 2^31 behind: 64 bits per group already)
   if (g < P.G) {
     if (mode == 1) {
       // cursor 0 never stalls and loses what the ring no longer holds: lo + n = min(cm, l)
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(256) void feed_emit_kernel(DevPlanes P, int raft, u
     s_rotb[tid] = rf.rotb;
     s_sb[tid] = rf.sb;
     s_sb2[tid] = rf.sb2;
-    s_shf[tid] = rf.shf;
+    s_shf[tid] = rf.sh ? rf.shf : -1;   // (-1: not in shared form; no index is negative)
   }
   uint32_t inc = n;
 #pragma unroll
@@ -249,7 +250,7 @@ __global__ __launch_bounds__(256) void feed_emit_kernel(DevPlanes P, int raft, u
       const int idx = s_lo[r][t] + 1 + int(q);
       const uint32_t gs = blockIdx.x * 256u + t;
       const uint32_t rw = s_rot[t];
-      const RingForm rf{rw & 0xFFFFu, rw >> 16, s_rotb[t], s_sb[t], s_sb2[t], s_shf[t]};
+      const RingForm rf{rw & 0xFFFFu, rw >> 16, s_rotb[t], s_sb[t], s_sb2[t], s_shf[t], s_shf[t] >= 0};
       const Entry e = canon_entry<R>(P, rf, gs, uint32_t(r), idx);
       const uint64_t gid = P.gbase + gs;
       w[0] = uint32_t(gid);

@@ -1263,7 +1263,9 @@ struct Group {
       AEReq q;
       q.term = lt; q.lc = lc;
       q.corrupt = corrupted(P, p);
-      const int nxt = m[p] + 1;                               // NextIndex == MatchIndex + 1
+      // NextIndex == MatchIndex + 1, in 64 bits like Go's int: at MatchIndex
+      // 2^31-1 it is above LastApplied and a heartbeat goes out
+      const int64_t nxt = int64_t(m[p]) + 1;
       int from = 1;
       if (nxt <= ll) {                                        // 341
         if (nxt == 1) {                                       // 343-351: whole log
@@ -1272,7 +1274,7 @@ struct Group {
           if (nxt < 1 || m[p] > ll) { raise(F_PANIC_GETLOG); return; }
           if (m[p] <= ll - int(P.K)) { raise(F_RING_EVICTED); return; }
           q.prev_term = term_at(P, c, m[p]);                  // GetLog(MatchIndex).Term
-          q.prev_idx = m[p]; q.n = ll - nxt + 1; from = nxt;
+          q.prev_idx = m[p]; q.n = ll - m[p]; from = m[p] + 1;
         }
       } else {                                                // 364-371: heartbeat
         q.n = 0; q.prev_idx = m[p]; q.prev_term = lt;
@@ -1448,6 +1450,8 @@ struct Group {
       if (gr) { ++count; ++st[S_VOTES]; }
     });
     if (alive() && !stop && role(c) == ROLE_C && 2 * count > R) {
+      // EXT: NextIndex = last + 1 would be 2^31 (RAFT_F_OVERFLOW): role and rows stay
+      if (cl >= I32MAX) { raise(F_OVERFLOW); return 0; }
       set_role(c, ROLE_L);
       int m[R], nx[R];
 #pragma unroll
@@ -1536,7 +1540,7 @@ struct Group {
       if (p == c || stop || !alive()) return;
       if (dropped(c, p)) { ++st[S_AE_FAIL]; return; }
       const int nxt = nx[p];
-      if (nxt < 1 || nxt > ll + 1) { raise(F_PANIC_GETLOG); return; }
+      if (nxt < 1 || nxt > int64_t(ll) + 1) { raise(F_PANIC_GETLOG); return; }
       if (nxt <= lh - K) { raise(F_RING_EVICTED); return; }
       AEReq q;
       q.term = lt; q.lc = lc;
@@ -1554,10 +1558,13 @@ struct Group {
       if (!alive()) return;
       if (a.term > lt) { r_observe_rt(T, c, a.term); ++st[S_AE_FAIL]; stop = true; return; }
       if (a.ok) {
+        // EXT: NextIndex = match + 1 would be 2^31: the follower has answered, c's rows and counters stay
+        if (a.match >= I32MAX) { raise(F_OVERFLOW); return; }
         m[p] = a.match; nx[p] = a.match + 1; dirty |= 1u << p;
         ++st[S_AE_OK];
       } else {
-        int nn = nx[p] - 1 < a.match + 1 ? nx[p] - 1 : a.match + 1;
+        // (hint + 1 in 64 bits: the hint may be 2^31-1, a same-term leader's LastApplied; the minimum fits)
+        int nn = nx[p] - 1 < int64_t(a.match) + 1 ? nx[p] - 1 : a.match + 1;
         nn = nn < 1 ? 1 : nn;
         if (nn != nx[p]) { nx[p] = nn; dirty |= 1u << p; }
         ++st[S_AE_FAIL];

@@ -437,13 +437,14 @@ struct Seg {
     int q_n = 0, q_prev = 0, j0 = 0;
     if (part) {
       // AppendEntries for this peer (main.go:341-372), NextIndex = MatchIndex+1
-      const int nxt = m + 1;
+      // (64-bit like Go's int: MatchIndex may be 2^31-1, then NextIndex > LastApplied and a heartbeat goes out)
+      const int64_t nxt = int64_t(m) + 1;
       int prev_term = lt;
       if (nxt <= ll) {
         if (nxt == 1) { q_n = ll; q_prev = 0; prev_term = lt; src.from = 1; }              // 343-351
         else if (nxt < 1 || m > ll) f = F_PANIC_GETLOG;
         else if (m <= ll - int(P.K)) f = F_RING_EVICTED;
-        else { prev_term = leader_term_at(P, c, ll, lltm, m); q_prev = m; q_n = ll - nxt + 1; src.from = nxt; }  // 353-360
+        else { prev_term = leader_term_at(P, c, ll, lltm, m); q_prev = m; q_n = ll - m; src.from = m + 1; }  // 353-360
       } else { q_n = 0; q_prev = m; prev_term = lt; }                                       // 364-371
       if (!f) {
         // Run (main.go:98-109) -> the receiver's handler
@@ -606,7 +607,7 @@ struct Seg {
     if (part) {
       const int nxt = nx;
       int prev_term = 0;
-      if (nxt < 1 || nxt > ll + 1) f = F_PANIC_GETLOG;
+      if (nxt < 1 || nxt > int64_t(ll) + 1) f = F_PANIC_GETLOG;
       else if (nxt <= lh - K) f = F_RING_EVICTED;
       else {
         q_prev = nxt - 1;
@@ -669,12 +670,16 @@ struct Seg {
       }
     }
     // the round stops at the first peer that faults or answers a higher term
+    // EXT: NextIndex = match + 1 would be 2^31 (RAFT_F_OVERFLOW): this follower has
+    // answered and keeps what it did, the leader's rows and counters stay
+    const bool ovf = part && !f && ok && match >= I32MAX;
+    if (ovf) f = F_OVERFLOW;
     const bool stop_me = part && (f != 0 || (rterm > lt));
     const uint32_t fm = mask(stop_me);
     const int ps = first_of(fm);
     if (me > ps) restore(sv);
     const bool done = part && me < ps;
-    if (done && ok) {
+    if ((done || (ovf && me == ps)) && ok) {
       if (copy) {
         const int tl = copy_entries(P, src, q_prev, jc, q_n);
         const int nl = q_prev + q_n;
@@ -705,7 +710,8 @@ struct Seg {
     if (done) {
       if (ok) { m = match; nx = match + 1; dm = dn = true; }
       else {
-        int nn = nx - 1 < match + 1 ? nx - 1 : match + 1;
+        // (hint + 1 in 64 bits: the hint may be 2^31-1, a same-term leader's LastApplied; the minimum fits)
+        int nn = nx - 1 < int64_t(match) + 1 ? nx - 1 : match + 1;
         nn = nn < 1 ? 1 : nn;
         if (nn != nx) { nx = nn; dm = dn = true; }
       }
@@ -764,6 +770,8 @@ struct Seg {
     const int count = 1 + __builtin_popcount(gm);
     stat_add(S_VOTES, __builtin_popcount(gm));
     if (alive() && !stop && bc(role, c) == ROLE_C && 2 * count > R) {
+      // EXT: NextIndex = last + 1 would be 2^31 (RAFT_F_OVERFLOW): role and rows stay
+      if (cl >= I32MAX) { raise(F_OVERFLOW); return 0; }
       if (me == c) set_role(ROLE_L);
       if (primary == NO_PRIMARY) primary = c;
       if (peer) {   // MatchIndex 0, NextIndex = last + 1 for every peer

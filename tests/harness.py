@@ -12,10 +12,15 @@ from raftstep import abi
 F, C, L = abi.FOLLOWER, abi.CANDIDATE, abi.LEADER
 
 
-def node(role=F, term=0, voted=0, log=(), commit=0, deadline=1000, timeout=20, match=None):
-    """One replica's state; log is a list of (term, value) = Node.Log (main.go:21)."""
+I32 = 2**31 - 1   # the largest term and log index the engine holds
+
+
+def node(role=F, term=0, voted=0, log=(), commit=0, deadline=1000, timeout=20, match=None, last=None):
+    """One replica's state; log is a list of (term, value) = Node.Log (main.go:21).
+    With last given, log holds only the entries last-len(log)+1..last (a log
+    near the int32 ceiling, of which the ring keeps the tail anyway)."""
     return dict(role=role, term=term, voted=voted, log=list(log), commit=commit,
-                deadline=deadline, timeout=timeout, match=match)
+                deadline=deadline, timeout=timeout, match=match, last=last)
 
 
 def build_state(groups_nodes, R, K, faults=None):
@@ -28,7 +33,10 @@ def build_state(groups_nodes, R, K, faults=None):
             st["role"][g, r] = n["role"]
             st["voted"][g, r] = n["voted"]
             st["term"][g, r] = n["term"]
-            st["last"][g, r] = len(n["log"])
+            last = len(n["log"]) if n.get("last") is None else n["last"]
+            first = last - len(n["log"]) + 1      # index of log[0]
+            assert first >= 1 and (first == 1 or len(n["log"]) >= K), "the ring's entries must be given"
+            st["last"][g, r] = last
             st["commit"][g, r] = n["commit"]
             st["deadline"][g, r] = n["deadline"]
             st["timeout"][g, r] = n["timeout"]
@@ -36,9 +44,8 @@ def build_state(groups_nodes, R, K, faults=None):
                 m = n["match"] or [0] * R
                 for p in range(R):
                     st["match"][g, r, p] = 0 if p == r else m[p]
-            last = len(n["log"])
             for i in range(max(1, last - K + 1), last + 1):
-                t, v = n["log"][i - 1]
+                t, v = n["log"][i - first]
                 st["log_term"][g, r, (i - 1) % K] = t
                 st["log_value"][g, r, (i - 1) % K] = v
         if faults is not None:
@@ -199,6 +206,57 @@ def random_state(rng, G, R, K, max_term=6, max_log=12):
                     if p != r:
                         st["match"][g, r, p] = rng.integers(0, max_log + 2)
     return st
+
+
+def ceiling_state(rng, G, R, K, raft=False):
+    """random_state at the top of the int32 range: terms (of replicas and of
+    entries) in I-5..I, last / commit / match in I-12..I. raft=True: RAFT
+    stores NextIndex = match + 1, and 2^31 is not one (raftstep.h,
+    RAFT_F_OVERFLOW), so match stops at I-1."""
+    st = abi.empty_state(G, R, K)
+    st["role"][:] = rng.integers(0, 3, (G, R))
+    st["voted"][:] = rng.integers(0, 2, (G, R))
+    st["term"][:] = rng.integers(I32 - 5, I32 + 1, (G, R))
+    st["last"][:] = rng.integers(I32 - 12, I32 + 1, (G, R))
+    st["commit"][:] = rng.integers(I32 - 12, I32 + 1, (G, R))
+    st["timeout"][:] = rng.integers(10, 30, (G, R))
+    st["deadline"][:] = rng.integers(0, 60, (G, R))
+    st["log_term"][:] = rng.integers(I32 - 5, I32 + 1, (G, R, K))   # last > K: every ring slot is live
+    st["log_value"][:] = rng.integers(0, 1 << 62, (G, R, K))
+    m = rng.integers(I32 - 12, I32 + (0 if raft else 1), (G, R, R))
+    lead = (st["role"] == L)[:, :, None] & ~np.eye(R, dtype=bool)[None]
+    st["match"][:] = np.where(lead, m, 0)
+    return st
+
+
+def lift_state(st, d_index, d_term, K):
+    """The state `st` moved up the log: d_index added to last, commit and hwm
+    and to the leaders' match and next rows (entries >= 1), ring slots rolled
+    by d_index mod K, d_term added to term and to the live entries' log_term,
+    CRCs restamped where the state has any. For the in-step states of the
+    shift-invariance test: no empty log, no CommitIndex of 0, and every
+    leader's match >= 1 (so next = match + 1 moves with it)."""
+    out = {k: np.array(v, copy=True) for k, v in st.items()}
+    G, R = st["last"].shape
+    assert (st["last"] > 0).all() and (st["commit"] > 0).all(), "lift_state: in-step states only"
+    for k in ("last", "commit", "hwm"):
+        out[k] = (st[k].astype(np.int64) + d_index).astype(np.int32)
+    for k in ("match", "next"):
+        out[k] = np.where(st[k] >= 1, st[k].astype(np.int64) + d_index, st[k]).astype(np.int32)
+    out["term"] = (st["term"].astype(np.int64) + d_term).astype(np.int32)
+    live = np.zeros(st["log_term"].shape, bool)
+    for g in range(G):
+        for r in range(R):
+            last, top = int(st["last"][g, r]), max(int(st["hwm"][g, r]), int(st["last"][g, r]))
+            for i in range(max(1, top - K + 1), last + 1):
+                live[g, r, (i - 1) % K] = True
+    lt = np.where(live, st["log_term"].astype(np.int64) + d_term, st["log_term"]).astype(np.int32)
+    for k, v in (("log_term", lt), ("log_value", st["log_value"]), ("log_crc", st["log_crc"])):
+        out[k] = np.roll(v, d_index % K, axis=2)
+    if st["log_crc"].any():
+        for g, r, s in np.argwhere(np.roll(live, d_index % K, axis=2)):
+            out["log_crc"][g, r, s] = entry_crc(int(out["log_term"][g, r, s]), int(out["log_value"][g, r, s]))
+    return out
 
 
 def staged_values(seed, t, n, E, groups):

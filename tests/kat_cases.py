@@ -366,8 +366,135 @@ def kat23_crc_reject(make):
     assert (st2["log_crc"][0, :, :3] == st2["log_crc"][0, 0, :3]).all()
 
 
+# ---- the top of the int32 range. I = 2^31-1 is the largest term and index the
+# engine holds; Go's int is 64-bit, so main.go itself goes on and the EXT rule
+# RAFT_F_OVERFLOW freezes the group where a value would leave int32. A "log at
+# I" is a replica with LastApplied == I whose ring holds the entries I-7..I.
+I = harness.I32
+STAT = abi.STAT_NAMES.index
+
+
+def _tail(last, term, K=K8):
+    """The ring's K entries last-K+1..last, all of `term`; Value = low byte of the index."""
+    return [(term, i & 0xFF) for i in range(last - K + 1, last + 1)]
+
+
+def _at(role, term, last, voted=1, **kw):
+    return node(role, term, voted, _tail(last, term), last=last, **kw)
+
+
+def kat24_leader_round_at_ceiling(make):
+    """MatchIndex == I: NextIndex = I+1 > LastApplied, so a heartbeat goes out
+    with PrevLogIndex = I, PrevLogTerm = Term (main.go:364-371). In step:
+    GetLog(I).Term matches -> Success, MatchIndex I, and CommitIndex =
+    min(LC, len+1) = LC, len+1 being 2^31 (151-152). Lagging by two:
+    LastApplied + 0 < PrevLogIndex -> false (137-140), MatchIndex stays. Once
+    as the handler op and once inside tick(), where the stats show 3 ok, 1 fail."""
+    def load(**kw):
+        e = _impl(make, 3, groups=2, **kw)
+        lead = dict(commit=I, match=[0, I, I])
+        # (followers' timers started before either call's time, 14 s and 18 s, as in any run: the
+        #  engine keeps a timer as its start, and a heartbeat moves a start forward only)
+        e.load_state(build_state([
+            [_at(L, 5, I, **lead), _at(F, 5, I, commit=I - 1, timeout=17, deadline=26), _at(F, 5, I, commit=I - 3, deadline=26)],
+            [_at(L, 5, I, **lead), _at(F, 5, I - 2, commit=I - 4, timeout=13, deadline=26), _at(F, 5, I, commit=I, deadline=26)],
+        ], 3, K8))
+        return e
+
+    def check(s, now):
+        assert (s["fault"] == 0).all()
+        assert (s["last"] == [[I, I, I], [I, I - 2, I]]).all() and (s["term"] == 5).all()
+        assert list(s["match"][0, 0]) == [0, I, I] and list(s["match"][1, 0]) == [0, I, I]
+        assert (s["commit"] == [[I, I, I], [I, I - 4, I]]).all()
+        # both the accepting and the refusing follower reset their timers first (124-127)
+        assert s["deadline"][0, 1] == 2 * now + 17 and s["deadline"][1, 1] == 2 * now + 13
+
+    e = load()
+    for g in (0, 1):
+        assert _op(e, 7, 0, abi.OP_LEADER_ROUND, group=g) == (0, 0, I)
+    check(e.store_state(), 7)
+    e = load(client_period=0)
+    st = e.tick(9, 1)
+    check(e.store_state(), 9)
+    exp = dict(ae_ok=3, ae_fail=1, faults=0, committed=0, leader_groups=2, term_bumps=0)
+    assert {k: int(st[STAT(k)]) for k in exp} == exp
+
+
+def kat25_append_entries_at_ceiling(make):
+    """raft_append_entries_batch on a follower at LastApplied == I-1 with a valid
+    prev: two entries would make len(Log) 2^31 -> RAFT_F_OVERFLOW, nothing is
+    appended, the timer was already reset (main.go:124-127); one entry with
+    LeaderCommit I -> LastApplied I, CommitIndex min(I, len+1) = I (148-152)."""
+    def load():
+        e = _impl(make, 3)
+        e.load_state(build_state([[_at(F, 3, I - 1, commit=I - 5, deadline=40, timeout=19), node(), node()]], 3, K8))
+        return e
+
+    e = load()
+    ok, _, fault = _ae(e, 4, 0, term=3, prev_idx=I - 1, prev_term=3, lc=I, logs=[(3, 0xA), (3, 0xB)])
+    assert (ok, fault) == (0, abi.F_OVERFLOW)
+    s = e.store_state()
+    assert s["fault"][0] == abi.F_OVERFLOW and s["last"][0, 0] == I - 1 and s["commit"][0, 0] == I - 5
+    assert log_of(s, 0, 0, K8) == _tail(I - 1, 3) and s["deadline"][0, 0] == 8 + 19
+    e = load()
+    assert _ae(e, 4, 0, term=3, prev_idx=I - 1, prev_term=3, lc=I, logs=[(3, 0xA)]) == (1, I, 0)
+    s = e.store_state()
+    assert s["fault"][0] == 0 and s["last"][0, 0] == I and s["commit"][0, 0] == I
+    assert log_of(s, 0, 0, K8) == _tail(I - 1, 3)[1:] + [(3, 0xA)]
+
+
+def kat26_client_append_runs_out_of_room(make):
+    """E = 3 client requests in one tick to a leader at LastApplied == I-1
+    (main.go:327-329 runs once per request): the first is appended, the second
+    would leave int32 -> RAFT_F_OVERFLOW, the group freezes with the leader at
+    I, before any round. With two leaders in the group the first one's fault
+    freezes the group: the second appends nothing. OP_CLIENT_APPEND at I faults."""
+    e = _impl(make, 3, groups=2, entries_per_tick=3, client_period=1)
+    m = [0, I - 1, I - 1]
+    e.load_state(build_state([
+        [_at(L, 4, I - 1, commit=I - 1, match=m), _at(F, 4, I - 1, commit=I - 2), _at(F, 4, I - 1, commit=I - 2)],
+        [_at(L, 4, I - 1, commit=I - 1, match=m), _at(L, 4, I - 1, commit=I - 1, match=[I - 1, 0, I - 1]),
+         _at(F, 4, I - 1, commit=I - 2)],
+    ], 3, K8))
+    st = e.tick(3, 1)
+    s = e.store_state()
+    assert list(s["fault"]) == [abi.F_OVERFLOW] * 2
+    assert (s["last"] == [[I, I - 1, I - 1]] * 2).all()
+    assert (s["commit"] == [[I - 1, I - 2, I - 2], [I - 1, I - 1, I - 2]]).all()
+    for g in (0, 1):
+        assert s["log_term"][g, 0, (I - 1) % K8] == 4 and list(s["match"][g, 0]) == m
+    assert [int(x) for x in st] == [0, 0, 0, 0, 0, 0, 2, 0]      # faults == one per group, nothing else
+    e = _impl(make, 3)
+    e.load_state(build_state([[_at(L, 4, I, match=[0, I, I]), _at(F, 4, I), _at(F, 4, I)]], 3, K8))
+    assert _op(e, 3, 0, abi.OP_CLIENT_APPEND, 99)[:2] == (0, abi.F_OVERFLOW)
+    s = e.store_state()
+    assert s["last"][0, 0] == I and log_of(s, 0, 0, K8) == _tail(I, 4)
+
+
+def kat27_terms_at_ceiling(make):
+    """Term++ (main.go:176 / 250) at Term == I -> RAFT_F_OVERFLOW. A follower at
+    I-1 whose timer fires inside tick() becomes a candidate at I (171-177), both
+    peers (Term I-1 <= I, not voted) grant and take Term I (157-170): Leader at
+    I; the next timeout of any replica then faults."""
+    e = _impl(make, 3)
+    e.load_state(build_state([[node(C, I, 1), node(F, I, 1), node(F, I, 1)]], 3, K8))
+    assert _op(e, 2, 0, abi.OP_TIMEOUT)[:2] == (0, abi.F_OVERFLOW)
+    assert e.store_state()["term"][0, 0] == I
+    e = _impl(make, 3, client_period=0)
+    e.load_state(build_state([[node(F, I - 1, 0, deadline=10), node(F, I - 1, 0), node(F, I - 1, 0)]], 3, K8))
+    st = e.tick(5, 1)                                # now = 10 s: replica 0's timer is due
+    s = e.store_state()
+    assert list(s["role"][0]) == [L, F, F] and list(s["term"][0]) == [I, I, I] and s["fault"][0] == 0
+    exp = dict(term_bumps=1, elections_won=1, votes_granted=2, faults=0, leader_groups=1)
+    assert {k: int(st[STAT(k)]) for k in exp} == exp
+    assert _op(e, 6, 1, abi.OP_TIMEOUT)[:2] == (0, abi.F_OVERFLOW)
+    s = e.store_state()
+    assert list(s["term"][0]) == [I, I, I] and list(s["role"][0]) == [L, F, F] and s["fault"][0] == abi.F_OVERFLOW
+
+
 ALL = [kat01_election, kat02_heartbeat_empty, kat03_first_entry, kat04_commit_propagates, kat05_suffix,
        kat06_commit_plus_one, kat07_10_commit_rule, kat11_panic_getlog, kat12_stale_term,
        kat13_candidate_steps_down, kat14_leader_steps_down, kat15_sticky_vote, kat16_prev_term_mismatch,
        kat17_deadlocks, kat18_edge_replicas, kat19_role_checks, kat20_ext_limits, kat21_tick_election,
-       kat22_tick_steady, kat23_crc_reject]
+       kat22_tick_steady, kat23_crc_reject, kat24_leader_round_at_ceiling, kat25_append_entries_at_ceiling,
+       kat26_client_append_runs_out_of_room, kat27_terms_at_ceiling]

@@ -165,5 +165,91 @@ def raft08_tick_steady(make):
     assert list(s) == [6 * N, 0, 0, 6 * 4 * N, 0, 0, 0, 6 * N]
 
 
+# ---- the top of the int32 range (I = 2^31-1). RAFT stores NextIndex in an
+# int32 plane, so an assignment that would store 2^31 freezes the group with
+# RAFT_F_OVERFLOW at that assignment (include/raftstep.h): the leader's or
+# candidate's rows and role stay as they were, what the peers did stays done.
+I = 2**31 - 1
+
+
+def _tail(last, term, K=K8):
+    return [(term, i & 0xFF) for i in range(last - K + 1, last + 1)]
+
+
+def _at(role, term, last, voted, **kw):
+    return node(role, term, voted, _tail(last, term), last=last, **kw)
+
+
+def raft09_next_index_overflow_on_success(make):
+    """nextIndex = matchIndex + 1 after a success at matchIndex == I: peer 1
+    takes the entry I and answers I; storing nextIndex 2^31 freezes the group.
+    The leader's rows keep their values and peer 2 is not reached."""
+    e = _impl(make, 3)
+    e.load_state(_state([_at(L, 5, I, 1, commit=I - 1, match=[0, I - 1, I - 1]), _at(F, 5, I - 1, 1, commit=I - 1),
+                         _at(F, 5, I - 1, 1, commit=I - 2)], 3, next_=[0, I, I]))
+    st, fault, _ = _op(e, 5, 0, abi.OP_LEADER_ROUND)
+    assert (st, fault) == (0, abi.F_OVERFLOW)
+    s = e.store_state()
+    assert s["fault"][0] == abi.F_OVERFLOW and list(s["last"][0]) == [I, I, I - 1]
+    assert list(s["match"][0, 0]) == [0, I - 1, I - 1] and list(s["next"][0, 0]) == [0, I, I]
+    assert list(s["commit"][0]) == [I - 1, I - 1, I - 2]     # LC = I-1 moves nobody
+    assert log_of(s, 0, 1, K8) == _tail(I, 5)
+
+
+def raft10_election_won_at_ceiling(make):
+    """Winning an election sets nextIndex = last + 1 for every peer; at last ==
+    I that is 2^31: the votes are granted (votedFor = 0 on both peers), the
+    candidate stays a candidate and the group freezes."""
+    e = _impl(make, 3)
+    e.load_state(_state([_at(C, 5, I, 1), _at(F, 5, I, NONE), _at(F, 5, I, NONE)], 3))
+    assert _op(e, 5, 0, abi.OP_CANDIDATE_ROUND) == (0, abi.F_OVERFLOW, 0)
+    s = e.store_state()
+    assert list(s["role"][0]) == [C, F, F] and list(s["voted"][0]) == [1, 1, 1] and s["fault"][0] == abi.F_OVERFLOW
+    assert (s["next"][0] == 0).all() and (s["match"][0] == 0).all()
+    # one entry lower the same election is won: nextIndex = I
+    e = _impl(make, 3)
+    e.load_state(_state([_at(C, 5, I - 1, 1), _at(F, 5, I - 1, NONE), _at(F, 5, I - 1, NONE)], 3))
+    assert _op(e, 5, 0, abi.OP_CANDIDATE_ROUND) == (0, 0, 1)
+    s = e.store_state()
+    assert list(s["role"][0]) == [L, F, F] and list(s["next"][0, 0]) == [0, I, I]
+
+
+def raft11_append_past_ceiling(make):
+    """prevLogIndex + len(entries) > I (raft_oracle.c r_deliver_ae) ->
+    RAFT_F_OVERFLOW before anything is appended; the timer was reset (the
+    request came from the current leader). Up to I exactly it is accepted."""
+    def load():
+        e = _impl(make, 3)
+        e.load_state(_state([_at(F, 3, I - 1, NONE, commit=I - 4, deadline=40, timeout=19), node(), node()], 3))
+        return e
+
+    e = load()
+    ok, _, term, fault = _ae(e, 4, 0, term=3, prev_idx=I - 1, prev_term=3, lc=I, logs=[(3, 1), (3, 2)])
+    assert (ok, term, fault) == (0, 3, abi.F_OVERFLOW)
+    s = e.store_state()
+    assert s["last"][0, 0] == I - 1 and s["commit"][0, 0] == I - 4 and s["deadline"][0, 0] == 8 + 19
+    assert log_of(s, 0, 0, K8) == _tail(I - 1, 3)
+    e = load()
+    assert _ae(e, 4, 0, term=3, prev_idx=I - 1, prev_term=3, lc=I, logs=[(3, 1)]) == (1, I, 3, 0)
+    s = e.store_state()
+    assert s["last"][0, 0] == I and s["commit"][0, 0] == I and s["hwm"][0, 0] == I
+
+
+def raft12_backoff_hint_at_ceiling(make):
+    """nextIndex backs off to min(nextIndex - 1, hint + 1). A same-term leader
+    (no election makes one; a loaded state may hold one) refuses with its own
+    length as the hint: at length I, hint + 1 is 2^31, and the minimum is
+    nextIndex - 1. Peer 2 takes the heartbeat; {I-2 (leader), 0, I-2} commits I-2."""
+    e = _impl(make, 3)
+    e.load_state(_state([_at(L, 5, I - 2, 1, commit=I - 3, match=[0, 0, 0]), _at(L, 5, I, 2, commit=I - 3, match=[0, 0, 0]),
+                         _at(F, 5, I - 2, 1, commit=I - 3)], 3, next_=[I - 3, I - 3, I - 1]))
+    assert _op(e, 5, 0, abi.OP_LEADER_ROUND) == (0, 0, I - 2)
+    s = e.store_state()
+    assert list(s["next"][0, 0]) == [0, I - 4, I - 1] and list(s["match"][0, 0]) == [0, 0, I - 2]
+    assert list(s["next"][0, 1]) == [I - 3, 0, I - 1] and list(s["role"][0]) == [L, L, F]
+    assert list(s["last"][0]) == [I - 2, I, I - 2] and list(s["commit"][0]) == [I - 2, I - 3, I - 3]
+
+
 ALL = [raft01_election, raft02_up_to_date, raft03_truncate, raft04_keep_matching, raft05_consistency_failures,
-       raft06_backoff_and_commit, raft07_step_down, raft08_tick_steady]
+       raft06_backoff_and_commit, raft07_step_down, raft08_tick_steady, raft09_next_index_overflow_on_success,
+       raft10_election_won_at_ceiling, raft11_append_past_ceiling, raft12_backoff_hint_at_ceiling]

@@ -434,6 +434,42 @@ int raft_store_groups(raft_engine* e, const uint64_t* groups, uint64_t n, raft_s
  * form until the next raft_init_steady. An open feed stays open: every fed
  * cursor of a restarted group becomes 0, the others do not move. */
 int raft_restart_groups(raft_engine* e, const uint64_t* groups, uint64_t n, int64_t tick0);
+/* The inverse of raft_store_groups: *v is the canonical view of groups[0..n)
+ * (local ids), indexed by the list position i with the per-group shapes of
+ * raft_store_groups, so what raft_store_groups(ids, n, &v) wrote can be passed
+ * back as it is (the rows of a checkpoint, a repaired row, a hand-made state).
+ * Fields: exactly raft_load_state's. role, voted, term, last, commit,
+ *   deadline, timeout, match, fault, log_term and log_value are required (no
+ *   partial patching: a missing one is RAFT_EINVAL); log_crc, next, hwm and
+ *   iso_victim are optional with the same derivations: an absent log_crc on a
+ *   payload_crc engine is stamped from (term, value), an absent or 0 next is
+ *   match + 1, an absent hwm or hwm < last is last, an absent iso_victim is 0.
+ * Validation: every listed row passes raft_load_state's range checks (fault
+ *   code; iso_victim nibbles 0 or 8 | replica < R; role <= Leader; voted <= 1
+ *   in REF, <= R in RAFT; last >= 0; timeout in 0..1023; RAFT: no derived
+ *   NextIndex of MatchIndex 2^31-1, last entry inside (hwm - K, hwm]); the
+ *   message names the list element and the group. Ids must be distinct
+ *   (RAFT_EINVAL) and < G (RAFT_ERANGE).
+ * Every argument error is found before anything is written: an error leaves
+ *   the state, the steady tick's forms and the feed as they were. n = 0
+ *   changes nothing. A poisoned engine answers RAFT_EINTERNAL.
+ * A listed group then holds exactly the state raft_load_state would give it
+ *   from the same rows: its canonical view and digest equal those of an
+ *   engine that loaded the whole view with these rows spliced in (it continues
+ *   on its own global id's trace). Every other group is untouched, bit for
+ *   bit, view and digest. The rows' timers are on the engine's own virtual
+ *   clock (as for raft_load_state): a timer start, deadline - timeout, after
+ *   the time of the engine's next tick outlives later heartbeats, since the
+ *   engine keeps the later of the two.
+ * Like a restart or a handler batch, the call ends the steady tick's list
+ *   skip and steady form until the next raft_init_steady. An open feed stays
+ *   open: every fed cursor of a loaded group becomes min(CommitIndex,
+ *   LastApplied) of that replica's loaded row (the restart's rule and
+ *   RAFT_FEED_FROM_COMMIT's, so the pair is never left stalled); the others
+ *   do not move.
+ * raft_load_state and raft_checkpoint_load write the state through the same
+ * device scatter, over every group (and, replacing the state, close the feed). */
+int raft_load_groups(raft_engine* e, const uint64_t* groups, uint64_t n, const raft_state_view* v);
 
 /* ---- multi-GPU statistics (RCCL over xGMI) -------------------------------
  * Groups shard by id (config.group_base); the only collective is the sum of

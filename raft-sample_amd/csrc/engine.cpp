@@ -80,11 +80,6 @@ uint32_t host_entry_crc(int32_t term, int64_t value) {
            T[768 + (hi & 255)] ^ T[512 + ((hi >> 8) & 255)] ^ T[256 + ((hi >> 16) & 255)] ^ T[hi >> 24]);
 }
 
-// Device ring layout (raft_device.hpp ring_tile / ring_in_tile): [Gp/64][K][64][R].
-inline uint64_t ring_index(uint64_t r, uint64_t g, uint64_t s, uint64_t K, uint64_t R) {
-  return (((g >> 6) * K + s) * 64 + (g & 63)) * R + r;
-}
-
 // RAFTSTEP_COMM_TIMEOUT_S: seconds a communicator's init or a call's
 // all-reduce may take before it fails with RAFT_ETIMEDOUT (default 300)
 double comm_timeout_s() {
@@ -577,20 +572,6 @@ int run_ops(raft_engine* e, int64_t now_tick, const std::vector<DevOp>& ops, con
   return RAFT_OK;
 }
 
-template <typename T>
-int h2d(raft_engine* e, T* d, const std::vector<T>& h) {
-  HIPCHK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, e->stream));
-  return RAFT_OK;
-}
-
-// Per-row host arrays [Gp][R] -> group records (row k of group g at
-// blk[g*recw + k*R ..], raft_device.hpp rix)
-void rec_put(std::vector<int32_t>& blk, int k, uint64_t R, uint64_t Gp, const std::vector<int32_t>& rows) {
-  const uint64_t W = recw_of(uint32_t(R));
-  for (uint64_t g = 0; g < Gp; ++g)
-    std::memcpy(&blk[g * W + uint64_t(k) * R], &rows[g * R], R * 4);
-}
-
 }  // namespace
 
 extern "C" {
@@ -956,8 +937,13 @@ struct ViewField {
   uint64_t per;
   void*& slot(raft_state_view& v) const { return *reinterpret_cast<void**>(reinterpret_cast<char*>(&v) + host); }
   void*& slot(GatherOut& o) const { return *reinterpret_cast<void**>(reinterpret_cast<char*>(&o) + dev); }
+  void*& slot(ScatterIn& o) const { return *reinterpret_cast<void**>(reinterpret_cast<char*>(&o) + dev); }
   size_t bytes() const { return size_t(elem) * per; }   // per group
 };
+// (ScatterIn mirrors GatherOut field for field: one offset serves both)
+static_assert(sizeof(ScatterIn) == sizeof(GatherOut) && offsetof(ScatterIn, log_term) == offsetof(GatherOut, log_term) &&
+                  offsetof(ScatterIn, iso_victim) == offsetof(GatherOut, iso_victim),
+              "ScatterIn and GatherOut layouts differ");
 std::vector<ViewField> view_fields(uint64_t R, uint64_t K) {
 #define VIEW_FIELD(f, elem, per) {#f, offsetof(raft_state_view, f), offsetof(GatherOut, f), elem, per}
   return {VIEW_FIELD(role, 1, R),         VIEW_FIELD(voted, 1, R),         VIEW_FIELD(term, 4, R),
@@ -1031,6 +1017,108 @@ int gather_view(raft_engine* e, uint64_t first, const uint32_t* ids, uint64_t n,
   return RAFT_OK;
 }
 
+// The fields a load needs (log_crc, next, hwm, iso_victim are derived when absent).
+bool view_complete(const raft_state_view* v) {
+  return v->role && v->voted && v->term && v->last && v->commit && v->deadline && v->timeout && v->match && v->fault &&
+         v->log_term && v->log_value;
+}
+
+// Range checks of rows [0, n) of a complete view before anything is written
+// (raft_load_state: row i is group i; raft_load_groups: groups[i]). What the
+// scatter kernels then store is derived on the device (scatter_view.hpp);
+// nothing here computes an internal word.
+int check_rows(const raft_engine* e, const raft_state_view* v, const uint64_t* groups, uint64_t n) {
+  const uint64_t R = e->cfg.replicas, K = e->cfg.ring_depth;
+  const bool raft = e->cfg.semantics == RAFT_SEM_RAFT;
+  const int max_vote = raft ? int(R) : 1;   // REF Voted bool; RAFT votedFor + 1
+  char buf[64];
+  uint64_t i = 0;
+  auto name = [&]() -> const char* {   // (only an error names its row)
+    if (groups) snprintf(buf, sizeof buf, "element %llu: group %llu", (unsigned long long)i, (unsigned long long)groups[i]);
+    else snprintf(buf, sizeof buf, "group %llu", (unsigned long long)i);
+    return buf;
+  };
+  for (; i < n; ++i) {
+    if (v->fault[i] > RAFT_F_OVERFLOW) return fail(RAFT_EINVAL, "%s: bad fault code", name());
+    if (v->iso_victim) {   // nibbles 0 or 8 | replica
+      const uint8_t x = v->iso_victim[i];
+      for (int sh = 0; sh < 8; sh += 4) {
+        const int nib = (x >> sh) & 0xF;
+        if (nib && (!(nib & 8) || uint32_t(nib & 7) >= R)) return fail(RAFT_EINVAL, "%s: bad iso_victim %#x", name(), x);
+      }
+    }
+    for (uint64_t r = 0; r < R; ++r) {
+      const uint64_t c = i * R + r;
+      if (v->role[c] > RAFT_LEADER || v->voted[c] > max_vote || v->last[c] < 0 || v->timeout[c] < 0 ||
+          v->timeout[c] > 1023)
+        return fail(RAFT_EINVAL, "%s replica %llu: field out of range", name(), (unsigned long long)r);
+      if (!raft) continue;
+      // (REF derives NextIndex at every use, in 64 bits, so MatchIndex 2^31-1 loads; RAFT stores
+      // it, and 2^31 is not a NextIndex: see RAFT_F_OVERFLOW)
+      if (v->role[c] == RAFT_LEADER)
+        for (uint64_t p = 0; p < R; ++p)
+          if (p != r && !(v->next && v->next[c * R + p] > 0) && v->match[c * R + p] == I32)
+            return fail(RAFT_EINVAL, "%s replica %llu: NextIndex of MatchIndex 2^31-1 does not fit", name(),
+                        (unsigned long long)r);
+      const int32_t h = (v->hwm && v->hwm[c] > v->last[c]) ? v->hwm[c] : v->last[c];
+      if (v->last[c] > 0 && int64_t(v->last[c]) <= int64_t(h) - int64_t(K))
+        return fail(RAFT_EINVAL, "%s replica %llu: last entry outside the ring window (hwm - K, hwm]", name(),
+                    (unsigned long long)r);
+    }
+  }
+  return RAFT_OK;
+}
+
+// The inverse of gather_view: rows [0, n) of *v (complete, checked) become
+// the state of groups ids[0..n) (distinct), or with ids null of the range
+// [first, first + n): chunk by chunk every present field is copied into
+// raft_engine::stage and the scatter kernels (k_groups.hip, scatter_view.hpp)
+// write the groups' words. The one writer of a loaded group. No entry
+// protocol: the callers run their own first. Ends with one synchronise.
+int scatter_view(raft_engine* e, uint64_t first, const uint32_t* ids, uint64_t n, const raft_state_view* v) {
+  if (!n) return RAFT_OK;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  const uint64_t R = e->cfg.replicas, K = e->cfg.ring_depth;
+  raft_state_view h = *v;
+  if (!e->cfg.payload_crc) h.log_crc = nullptr;   // (no stamp ring to write)
+  const std::vector<ViewField> fields = view_fields(R, K);
+  size_t per = 0;
+  for (const ViewField& f : fields)
+    if (f.slot(h)) per += f.bytes();
+  // chunks of groups bound the staging, as in gather_view: the ids, then each field's rows of one chunk
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const uint64_t chunk = std::min<uint64_t>(n, std::max<uint64_t>(256, (uint64_t(32) << 20) / per));
+  const size_t b_ids = ids ? al(size_t(n) * 4) : 0;
+  size_t need = b_ids;
+  for (const ViewField& f : fields)
+    if (f.slot(h)) need += al(f.bytes() * chunk);
+  if (int rc = ensure_stage(e, need)) return rc;
+  char* base = static_cast<char*>(e->stage);
+  uint32_t* d_ids = reinterpret_cast<uint32_t*>(base);
+  ScatterIn in{};
+  size_t off = b_ids;
+  for (const ViewField& f : fields) {
+    if (!f.slot(h)) continue;
+    f.slot(in) = base + off;
+    off += al(f.bytes() * chunk);
+  }
+  if (ids) HIPCHK(hipMemcpyAsync(d_ids, ids, size_t(n) * 4, hipMemcpyHostToDevice, e->stream));
+  const int raft = e->cfg.semantics == RAFT_SEM_RAFT;
+  for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
+    const uint64_t nc = std::min<uint64_t>(chunk, n - c0);
+    // (the stream orders this chunk's copies after the last chunk's kernels reading the same buffers;
+    // the caller's memory is pageable, so each copy has left it when the call returns)
+    for (const ViewField& f : fields)
+      if (f.slot(h))
+        HIPCHK(hipMemcpyAsync(f.slot(in), static_cast<const char*>(f.slot(h)) + c0 * f.bytes(),
+                              nc * f.bytes(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_scatter(e->R, e->P, raft, uint32_t(first + c0), ids ? d_ids + c0 : nullptr, uint32_t(nc), in,
+                          e->feed_mask ? e->feed_cur : nullptr, e->feed_mask, e->feed_nm, e->stream));
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return RAFT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1055,129 +1143,9 @@ int raft_store_state_range(raft_engine* e, uint64_t first_group, uint64_t n_grou
 int raft_load_state(raft_engine* e, const raft_state_view* v) {
   if (e) state_replacing(e);
   if (!e || !v) return fail(RAFT_EINVAL, "null argument");
-  if (!v->role || !v->voted || !v->term || !v->last || !v->commit || !v->deadline || !v->timeout ||
-      !v->match || !v->fault || !v->log_term || !v->log_value)
-    return fail(RAFT_EINVAL, "raft_load_state needs every field of the view");
-  HIPCHK(hipSetDevice(e->cfg.device));
-  const uint64_t R = e->cfg.replicas, G = e->cfg.groups, Gp = e->Gp, K = e->cfg.ring_depth;
-  const uint64_t KP = e->KP;
-  std::vector<int32_t> term(R * Gp, 0), last(R * Gp, 0), commit(R * Gp, 0), ts(R * Gp, 0), lm(R * Gp, 0),
-      xm(R * R * Gp, 0), lt(R * KP * Gp, 0), hb(Gp, HB_NONE);
-  std::vector<int32_t> rs(R * Gp, 0);
-  std::vector<uint16_t> meta(Gp, uint16_t(NO_PRIMARY));
-  std::vector<uint8_t> giso(Gp, 0);
-  std::vector<int64_t> lv(R * KP * Gp, 0);
-  std::vector<int32_t> ltm(R * Gp, 0);
-  std::vector<uint32_t> lcrc(e->cfg.payload_crc ? R * KP * Gp : 0, 0);
-  const bool raft = e->cfg.semantics == RAFT_SEM_RAFT;
-  std::vector<int32_t> ln(raft ? R * Gp : 0, 0), xn(raft ? R * R * Gp : 0, 0), hw(raft ? R * Gp : 0, 0);
-  const int max_vote = raft ? int(R) : 1;   // REF Voted bool; RAFT votedFor + 1
-  for (uint64_t g = 0; g < G; ++g) {
-    if (v->fault[g] > RAFT_F_OVERFLOW) return fail(RAFT_EINVAL, "group %llu: bad fault code", (unsigned long long)g);
-    if (v->iso_victim) {   // nibbles 0 or 8 | replica
-      const uint8_t x = v->iso_victim[g];
-      for (int sh = 0; sh < 8; sh += 4) {
-        const int nib = (x >> sh) & 0xF;
-        if (nib && (!(nib & 8) || uint32_t(nib & 7) >= R))
-          return fail(RAFT_EINVAL, "group %llu: bad iso_victim %#x", (unsigned long long)g, x);
-      }
-      giso[g] = x;
-    }
-    int primary = NO_PRIMARY;
-    for (uint64_t r = 0; r < R; ++r) {
-      const uint64_t c = g * R + r;
-      if (v->role[c] > RAFT_LEADER || v->voted[c] > max_vote || v->last[c] < 0 || v->timeout[c] < 0 ||
-          v->timeout[c] > 1023)
-        return fail(RAFT_EINVAL, "group %llu replica %llu: field out of range", (unsigned long long)g,
-                    (unsigned long long)r);
-      if (v->role[c] == RAFT_LEADER && primary == NO_PRIMARY) primary = int(r);
-    }
-    bool steady = primary != NO_PRIMARY;
-    for (uint64_t r = 0; r < R; ++r)
-      if (int(r) != primary && v->role[g * R + r] != RAFT_FOLLOWER) steady = false;
-    meta[g] = uint16_t(primary | (v->fault[g] << 4) | (steady ? M_STEADY : 0));
-    for (uint64_t r = 0; r < R; ++r) {
-      const uint64_t d = g * R + r, c = g * R + r;   // per-replica planes are group-major (rix)
-      term[d] = v->term[c];
-      last[d] = v->last[c];
-      commit[d] = v->commit[c];
-      ts[d] = v->deadline[c] - v->timeout[c];
-      rs[d] = int32_t(v->role[c] | (v->voted[c] << 2) | (uint32_t(v->timeout[c]) << 6));
-      if (v->role[c] == RAFT_LEADER)
-        for (uint64_t p = 0; p < R; ++p) {
-          if (p == r) continue;
-          const int32_t m = v->match[c * R + p];
-          // RAFT: NextIndex as given, 0/absent derives match+1 (the oracle's rule)
-          // (REF derives it at every use, in 64 bits, so MatchIndex 2^31-1 loads; RAFT stores
-          // it, and 2^31 is not a NextIndex: see RAFT_F_OVERFLOW)
-          const int64_t nx64 = (v->next && v->next[c * R + p] > 0) ? int64_t(v->next[c * R + p]) : int64_t(m) + 1;
-          if (raft && nx64 > 2147483647)
-            return fail(RAFT_EINVAL, "group %llu replica %llu: NextIndex of MatchIndex 2^31-1 does not fit",
-                        (unsigned long long)g, (unsigned long long)r);
-          const int32_t nx = raft ? int32_t(nx64) : 0;
-          if (int(r) == primary) {
-            lm[g * R + p] = m;
-            if (raft) ln[g * R + p] = nx;
-          } else {
-            xm[(r * R + p) * Gp + g] = m;
-            if (raft) xn[(r * R + p) * Gp + g] = nx;
-          }
-        }
-      if (raft) {
-        const int32_t h = (v->hwm && v->hwm[c] > v->last[c]) ? v->hwm[c] : v->last[c];
-        if (v->last[c] > 0 && int64_t(v->last[c]) <= int64_t(h) - int64_t(K))
-          return fail(RAFT_EINVAL, "group %llu replica %llu: last entry outside the ring window (hwm - K, hwm]",
-                      (unsigned long long)g, (unsigned long long)r);
-        hw[d] = h;
-      }
-      // view slot s = (idx-1) mod K; loaded rings use rotation 0 (physical slot (idx-1) mod KP).
-      // With KP == K every slot is copied as is; with KP = 2K only the entries the view
-      // holds for indices <= LastApplied (the others can never be read).
-      const int64_t l = v->last[c];
-      for (uint64_t s = 0; s < K; ++s) {
-        uint64_t ps = s;
-        if (KP != K) {
-          const int64_t idx = l >= 1 ? l - ((l - 1 - int64_t(s)) & int64_t(K - 1)) : 0;
-          if (idx < 1) continue;
-          ps = uint64_t(idx - 1) & (KP - 1);
-        }
-        const uint64_t o = ring_index(r, g, ps, KP, R);
-        lt[o] = v->log_term[c * K + s];
-        lv[o] = v->log_value[c * K + s];
-        if (e->cfg.payload_crc)
-          lcrc[o] = v->log_crc ? v->log_crc[c * K + s] : host_entry_crc(v->log_term[c * K + s], v->log_value[c * K + s]);
-      }
-      if (v->last[c] > 0) ltm[d] = v->log_term[c * K + uint64_t((v->last[c] - 1) & int64_t(K - 1))];
-    }
-  }
-  std::vector<int32_t> blk(Gp * recw_of(R), 0);   // group records
-  rec_put(blk, PL_TERM, R, Gp, term);
-  rec_put(blk, PL_LAST, R, Gp, last);
-  rec_put(blk, PL_COMMIT, R, Gp, commit);
-  rec_put(blk, PL_TSTART, R, Gp, ts);
-  rec_put(blk, PL_LTERM, R, Gp, ltm);
-  rec_put(blk, PL_RS, R, Gp, rs);
-  rec_put(blk, PL_LMATCH, R, Gp, lm);
-  if (raft) rec_put(blk, PL_LNEXT, R, Gp, ln);
-  if (raft) rec_put(blk, PL_HWM, R, Gp, hw);
-  int rc = RAFT_OK;
-  if (!rc) rc = h2d(e, e->P.rec, blk);
-  if (!rc) rc = h2d(e, e->P.hb, hb);
-  if (!rc) rc = h2d(e, e->P.xmatch, xm);
-  if (!rc) rc = h2d(e, e->P.gmeta, meta);
-  const std::vector<GSeg> cold(Gp, GSeg{});   // loaded rings: rotation 0, one segment
-  if (!rc) rc = h2d(e, e->P.gseg, cold);
-  if (!rc) rc = h2d(e, e->giso_plane, giso);   // the isolation victims
-  const std::vector<uint16_t> rot(Gp, 0);
-  const std::vector<int32_t> sb0(Gp, 0);
-  if (!rc) rc = h2d(e, e->P.grot, rot);
-  if (!rc) rc = h2d(e, e->P.gsb, sb0);
-  if (!rc && raft) rc = h2d(e, e->P.xnext, xn);
-  if (!rc && e->cfg.payload_crc) rc = h2d(e, e->P.log_crc, lcrc);
-  if (!rc) rc = h2d(e, e->P.log_term, lt);
-  if (!rc) rc = h2d(e, e->P.log_value, lv);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(e->stream));
+  if (!view_complete(v)) return fail(RAFT_EINVAL, "raft_load_state needs every field of the view");
+  if (int rc = check_rows(e, v, nullptr, e->cfg.groups)) return rc;
+  if (int rc = scatter_view(e, 0, nullptr, e->cfg.groups, v)) return rc;
   state_replaced(e);
   return RAFT_OK;
 }
@@ -2658,6 +2626,31 @@ int raft_restart_groups(raft_engine* e, const uint64_t* groups, uint64_t n, int6
                         e->feed_nm, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return RAFT_OK;
+}
+
+// The restart's route (settle_check, ring_flush, host_mutation) for the same
+// reasons: the loaded groups' new words clear ROT_SH and M_VX, and they leave
+// the compressed steady state the list skip and the steady form are proven
+// for. Every argument error is found before anything is written.
+int raft_load_groups(raft_engine* e, const uint64_t* groups, uint64_t n, const raft_state_view* v) {
+  if (!e || !v || (n && !groups)) return fail(RAFT_EINVAL, "null argument");
+  const uint64_t G = e->cfg.groups;
+  for (uint64_t i = 0; i < n; ++i)
+    if (groups[i] >= G)
+      return fail(RAFT_ERANGE, "raft_load_groups: element %llu: group %llu outside the engine's %llu",
+                  (unsigned long long)i, (unsigned long long)groups[i], (unsigned long long)G);
+  if (n) {
+    if (int rc = check_distinct(e, groups, sizeof(uint64_t), size_t(n))) return rc;
+    if (!view_complete(v)) return fail(RAFT_EINVAL, "raft_load_groups needs every field of the view but the optional ones");
+    if (int rc = check_rows(e, v, groups, n)) return rc;
+  }
+  if (int rc = settle_check(e)) return rc;
+  if (!n) return RAFT_OK;
+  std::vector<uint32_t> ids(n);
+  for (uint64_t i = 0; i < n; ++i) ids[i] = uint32_t(groups[i]);
+  if (int rc = ring_flush(e)) return rc;
+  host_mutation(e);
+  return scatter_view(e, 0, ids.data(), n, v);
 }
 
 }  // extern "C"

@@ -21,7 +21,14 @@
 // group for the logs. Every host read of the view goes through it
 // (raft_store_state / _range / _groups, raft_nodelog).
 // Restart: init_new_group (tick_common.hpp) for g = ids[i], feed cursors to 0.
+// Scatter: the inverse of the gather, the one writer of a loaded group
+// (raft_load_groups, raft_load_state, raft_checkpoint_load): the view's rows
+// in a staging buffer, indexed by list position, become the internal words of
+// ids[0..n) or of the range [first, first + n) (scatter_view.hpp); one lane
+// per listed group for the per-group words, one wave per listed group for its
+// ring tile column. Distinct ids: no two lanes or waves store the same word.
 #include "canon_view.hpp"
+#include "scatter_view.hpp"
 
 namespace raftstep {
 
@@ -184,6 +191,102 @@ __global__ __launch_bounds__(256) void restart_kernel(DevPlanes P, Trace T, cons
     for (uint32_t k = 0; k < nm; ++k) cur[size_t(g) * nm + k] = 0;
 }
 
+// Every per-group word of listed group i < n but its ring column, one lane
+// each (ids null: the range g = first + i): the record rows, gmeta, hb, the
+// cold ring words, giso, the leaders' match / next rows (the primary's in the
+// record, every further leader's in xmatch / xnext and 0 in every other row
+// there) and, with cur, the open feed's cursors of the group. The term of a
+// replica's last entry (lterm) is read from the view's log_term row here.
+template <int R>
+__global__ __launch_bounds__(256) void scatter_scalar_kernel(DevPlanes P, int raft, uint32_t first, const uint32_t* ids,
+                                                             uint32_t n, ScatterIn in, int32_t* cur, uint32_t mask,
+                                                             uint32_t nm) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t g = ids ? ids[i] : first + i;
+  const uint32_t K = P.K;
+  int primary = NO_PRIMARY;
+#pragma unroll 1
+  for (int r = R - 1; r >= 0; --r)
+    if (in.role[i * uint32_t(R) + uint32_t(r)] == uint8_t(ROLE_L)) primary = r;
+  bool steady = primary != NO_PRIMARY;
+  uint32_t ck = 0;
+#pragma unroll 1
+  for (int r = 0; r < R; ++r) {
+    const uint32_t k = i * uint32_t(R) + uint32_t(r);
+    const uint32_t x = rix<R>(g, r);
+    const uint32_t role = in.role[k];
+    const int32_t last = in.last[k], commit = in.commit[k], timeout = in.timeout[k];
+    if (r != primary && role != uint32_t(ROLE_F)) steady = false;
+    at(P.term, x) = in.term[k];
+    at(P.last, x) = last;
+    at(P.commit, x) = commit;
+    at(P.tstart, x) = scat_tstart(in.deadline[k], timeout);
+    at(P.lterm, x) = last > 0 ? in.log_term[size_t(k) * K + scat_last_slot(last, K)] : 0;
+    at(P.rs, x) = scat_rs(role, in.voted[k], timeout);
+    if (raft) at(P.hwm, x) = scat_hwm(in.hwm, k, last);
+    // the primary's row for peer r (0: no primary, or r is the primary itself)
+    const bool prow_live = primary != NO_PRIMARY && r != primary;
+    const size_t pk = (size_t(i) * R + uint32_t(prow_live ? primary : 0)) * R + uint32_t(r);
+    const int32_t pm = prow_live ? in.match[pk] : 0;
+    at(P.lmatch, x) = pm;
+    if (raft) at(P.lnext, x) = prow_live ? scat_next(in.next, pk, pm) : 0;
+    // replica r's own row: live for a further leader, 0 otherwise
+    const bool xrow = role == uint32_t(ROLE_L) && r != primary;
+#pragma unroll 1
+    for (int p = 0; p < R; ++p) {
+      const size_t xk = size_t(k) * R + uint32_t(p);
+      const bool live = xrow && p != r;
+      const int32_t m = live ? in.match[xk] : 0;
+      at(prow(P.xmatch, r * R + p, P.Gp), g) = m;
+      if (raft) at(prow(P.xnext, r * R + p, P.Gp), g) = live ? scat_next(in.next, xk, m) : 0;
+    }
+    if (cur && ((mask >> r) & 1u)) cur[size_t(g) * nm + ck++] = scat_cursor(commit, last);
+  }
+  at(P.gmeta, g) = scat_meta(primary, in.fault[i], steady);
+  at(P.hb, g) = HB_NONE;
+  at(P.giso, g) = in.iso_victim ? in.iso_victim[i] : uint8_t(0);
+  P.gseg[g] = GSeg{};   // (grota, grotb, gsb2, gshf: the cold words)
+  at(P.grot, g) = 0;
+  at(P.gsb, g) = 0;
+}
+
+// The ring tile column of listed groups, one wave per group: lane j of a pass
+// is (physical slot, replica) = (j / R, j % R), so the wave stores runs of R
+// contiguous words, 64 R words apart (the gather's reads mirrored), and reads
+// R input rows at consecutive slots. Every physical slot of the column is
+// written: the entry scat_view_slot names for it, else 0 (term, value, stamp).
+// Stamps (P.crc_on): the view's, or without log_crc computed from the CRC
+// table the tick kernels use.
+template <int R>
+__global__ __launch_bounds__(256) void scatter_log_kernel(DevPlanes P, uint32_t first, const uint32_t* ids, uint32_t n,
+                                                          ScatterIn in) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (i >= n) return;   // (wave-uniform)
+  const uint32_t g = ids ? ids[i] : first + i;
+  const uint32_t K = P.K, KP = P.KP, RKP = uint32_t(R) * KP;
+  const uint64_t rb = ring_tile(g, KP, R);
+  const size_t ib = size_t(i) * R * K;
+  for (uint32_t j = lane; j < RKP; j += 64u) {
+    const uint32_t ps = j / uint32_t(R), r = j - ps * uint32_t(R);
+    const int s = scat_view_slot(ps, in.last[i * uint32_t(R) + r], K, KP);
+    int32_t t = 0;
+    int64_t v = 0;
+    uint32_t c = 0;
+    if (s >= 0) {
+      const size_t k = ib + size_t(r) * K + uint32_t(s);
+      t = in.log_term[k];
+      v = in.log_value[k];
+      if (P.crc_on) c = in.log_crc ? in.log_crc[k] : crc_entry(P.crc_tab, t, v);
+    }
+    const uint32_t q = ring_in_tile(g, R, ps, r);
+    at(P.log_term + rb, q) = t;
+    at(P.log_value + rb, q) = v;
+    if (P.crc_on) at(P.log_crc + rb, q) = c;
+  }
+}
+
 hipError_t launch_group_count(int R, const DevPlanes& P, uint32_t select, uint32_t first, uint32_t* bsum, hipStream_t s) {
   const uint32_t b0 = first >> 8, nb = uint32_t((P.G + 255) / 256) - b0;
   RAFT_DISPATCH_R(R, hipLaunchKernelGGL(group_count_kernel<RR>, dim3(nb), dim3(256), 0, s, P, select, first, b0, bsum));
@@ -208,6 +311,14 @@ hipError_t launch_gather(int R, const DevPlanes& P, int raft, uint32_t first, co
     RAFT_DISPATCH_R(R, hipLaunchKernelGGL(gather_log_kernel<RR>, dim3((n + 3u) / 4u), dim3(256), 0, s, P, raft, first, ids,
                                           n, o, bad));
   }
+  return hipGetLastError();
+}
+hipError_t launch_scatter(int R, const DevPlanes& P, int raft, uint32_t first, const uint32_t* ids, uint32_t n,
+                          const ScatterIn& in, int32_t* cursors, uint32_t mask, uint32_t nm, hipStream_t s) {
+  RAFT_DISPATCH_R(R, hipLaunchKernelGGL(scatter_scalar_kernel<RR>, grid_for(n), dim3(256), 0, s, P, raft, first, ids, n, in,
+                                        cursors, mask, nm));
+  if (hipError_t rc = hipGetLastError()) return rc;
+  RAFT_DISPATCH_R(R, hipLaunchKernelGGL(scatter_log_kernel<RR>, dim3((n + 3u) / 4u), dim3(256), 0, s, P, first, ids, n, in));
   return hipGetLastError();
 }
 hipError_t launch_restart(int R, const DevPlanes& P, const Trace& T, const uint32_t* ids, uint32_t n, int32_t* cursors,

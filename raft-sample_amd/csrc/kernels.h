@@ -234,6 +234,28 @@ struct GatherOut {
 };
 hipError_t launch_gather(int R, const DevPlanes& P, int raft, uint32_t first, const uint32_t* ids, uint32_t n,
                          const GatherOut& o, uint32_t* bad, hipStream_t s);
+// The inverse: the canonical view of the distinct groups ids[0..n), or with
+// ids null of the range [first, first + n), in device buffers of the view's
+// layout indexed by list position, becomes those groups' internal words
+// (derived in scatter_view.hpp): what raft_load_state gives a group from the
+// same rows. role, voted, term, last, commit, deadline, timeout, match, fault,
+// log_term and log_value are required; log_crc, next, hwm and iso_victim may
+// be null (stamps computed with payload_crc, match + 1, last, 0). The rows are
+// range-checked by the host before the launch. cursors (may be null): the open
+// commit feed's, [G][nm] over the replicas of mask; the listed groups' become
+// min(CommitIndex, LastApplied) of the loaded rows.
+struct ScatterIn {
+  const uint8_t *role, *voted;
+  const int32_t *term, *last, *commit, *deadline, *timeout, *match;
+  const uint8_t* fault;
+  const int32_t* log_term;
+  const int64_t* log_value;
+  const uint32_t* log_crc;
+  const int32_t *next, *hwm;
+  const uint8_t* iso_victim;
+};
+hipError_t launch_scatter(int R, const DevPlanes& P, int raft, uint32_t first, const uint32_t* ids, uint32_t n,
+                          const ScatterIn& in, int32_t* cursors, uint32_t mask, uint32_t nm, hipStream_t s);
 // NewNode x R (init_new_group) for the distinct groups ids[0..n); cursors (may
 // be null): the open commit feed's, [G][nm], set to 0 for those groups.
 hipError_t launch_restart(int R, const DevPlanes& P, const Trace& T, const uint32_t* ids, uint32_t n, int32_t* cursors,

@@ -255,6 +255,7 @@ SIGNATURES = {
     "raft_group_scan": (C.c_int, [P, C.c_uint32, C.c_uint64, P, C.c_uint64, P]),
     "raft_store_groups": (C.c_int, [P, P, C.c_uint64, P]),
     "raft_restart_groups": (C.c_int, [P, P, C.c_uint64, C.c_int64]),
+    "raft_load_groups": (C.c_int, [P, P, C.c_uint64, P]),
 }
 
 
@@ -263,7 +264,7 @@ SIGNATURES = {
 # (and the commit feed and the group directory, added later still)
 OPTIONAL = ("raft_debug_diag_mode", "raft_stream_probe", "raft_engine_features",
             "raft_feed_open", "raft_feed_poll", "raft_feed_cursors", "raft_feed_close",
-            "raft_group_scan", "raft_store_groups", "raft_restart_groups")
+            "raft_group_scan", "raft_store_groups", "raft_restart_groups", "raft_load_groups")
 FEATURE_SHARED_ENTRIES, FEATURE_VIRTUAL_SUFFIXES = 1, 2   # raft_engine_features (include/raftstep.h)
 PROBE_PLAIN_RING, PROBE_NT_RECORD, PROBE_NO_HEARTBEAT = 1, 2, 4   # raft_stream_probe flags
 

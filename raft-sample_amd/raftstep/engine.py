@@ -253,6 +253,15 @@ class Engine:
         ids = self._ids(ids)
         _check(self.lib.raft_restart_groups(self.h, _ptr(ids), len(ids), int(tick0)))
 
+    def load_groups(self, ids, rows):
+        """Load the canonical view `rows` (what store_groups(ids) returns:
+        indexed by list position, optional fields may be absent) into the
+        listed (distinct) groups (raft_load_groups)."""
+        ids = self._ids(ids)
+        rows = abi.coerce_state(rows, len(ids), self.cfg.replicas, self.cfg.ring_depth)
+        v = abi.make_view(rows)
+        _check(self.lib.raft_load_groups(self.h, _ptr(ids), len(ids), C.byref(v)))
+
     # -- the fused tick ------------------------------------------------
     def tick(self, first_tick, nticks=1, stats=True):
         if stats:

@@ -471,6 +471,82 @@ int raft_restart_groups(raft_engine* e, const uint64_t* groups, uint64_t n, int6
  * device scatter, over every group (and, replacing the state, close the feed). */
 int raft_load_groups(raft_engine* e, const uint64_t* groups, uint64_t n, const raft_state_view* v);
 
+/* ---- group audit ----------------------------------------------------------
+ * Is the state the engine holds a correct Raft state? A read-only device pass
+ * that evaluates six safety invariants per group on the canonical view and
+ * reports the violating groups, each with a witness: the operator's look at a
+ * whole cluster (main.go:399-401 nodelog prints one node), and the one place
+ * where a CRC32C is recomputed from the entry bytes that sit in device memory.
+ * It reads the state as raft_group_scan does: no group leaves its shared
+ * form, the steady tick's forms stay, an open feed is left alone. Frozen
+ * groups are audited like any other.
+ *
+ * For replica r of a group (K = ring_depth):
+ *   top_r = max(hwm_r, last_r)           (REF: last_r)
+ *   lo_r  = max(1, top_r - K + 1)
+ *   the live indices of r are lo_r .. last_r (none when last_r < lo_r);
+ *   the common window of a pair a < b is max(lo_a, lo_b) .. min(last_a, last_b);
+ *   two entries are equal when Term and Value are equal (stamps are not compared);
+ *   "smallest pair" is the lexicographically smallest (a, b).
+ * The checks (witness: a, b, index of the record):
+ *   RAFT_AUDIT_TWO_LEADERS        replicas a < b are both Leader with equal Term
+ *       (election safety). Witness: the smallest pair, index = that Term.
+ *   RAFT_AUDIT_LOG_MATCHING       a pair has i <= j in its common window with
+ *       log_term_a[j] == log_term_b[j] and the entries at i unequal: its smallest
+ *       unequal index is <= its largest index with equal terms (log matching).
+ *       Witness: the smallest violating pair, index = its smallest unequal index.
+ *   RAFT_AUDIT_COMMIT_DIVERGED    a pair's smallest unequal index in the common
+ *       window is <= min(commit_a, commit_b) (committed prefixes agree).
+ *       Witness: the smallest violating pair and that index.
+ *   RAFT_AUDIT_TERM_ORDER         a replica has a live i > lo_r with
+ *       log_term[i] < log_term[i-1], or log_term[last_r] > term_r with a
+ *       non-empty window. Witness: the smallest such replica, b = 0xFF, index =
+ *       the smallest such i, last_r where there is none.
+ *   RAFT_AUDIT_STAMP              payload_crc engines: a live entry's stamp
+ *       differs from CRC32C(Term 4 B LE || Value 8 B LE), recomputed from the
+ *       stored term and value. Witness: the smallest such replica, b = 0xFF, the
+ *       smallest index. Without payload_crc the check is accepted and never violated.
+ *   RAFT_AUDIT_COMMIT_BEYOND_LOG  commit_r > last_r. REF follows the reference
+ *       here: a follower sets CommitIndex = min(LeaderCommit, LastApplied + 1)
+ *       (main.go:152), so last + 1 is a legal REF state the audit makes visible
+ *       (the commit feed waits for that entry); in RAFT it is a violation.
+ *       Witness: the smallest such replica, b = 0xFF, index = commit_r.
+ * Only the requested checks are evaluated. A group with at least one violated
+ * check is a hit; hits come in ascending group order and `cap`, info->matched,
+ * written and next_group follow raft_group_scan's contract (cap = 0 only
+ * counts, out may then be NULL; next_group = the local id after the last hit
+ * written, G when nothing is left, first_group when nothing was written and
+ * hits are left). info->per_check[k] = groups of the range that violate check
+ * bit k. The same state gives the same bytes.
+ * RAFT_EINVAL: checks 0 or with unknown bits, cap > 0 without out;
+ * RAFT_ERANGE: first_group > G (first_group == G is an empty audit). A
+ * poisoned engine answers RAFT_EINTERNAL. The first audit allocates 8 B per
+ * group on the device (counted by raft_engine_info), freed with the engine. */
+enum raft_audit_check {
+  RAFT_AUDIT_TWO_LEADERS       = 1u,
+  RAFT_AUDIT_LOG_MATCHING      = 2u,
+  RAFT_AUDIT_COMMIT_DIVERGED   = 4u,
+  RAFT_AUDIT_TERM_ORDER        = 8u,
+  RAFT_AUDIT_STAMP             = 16u,
+  RAFT_AUDIT_COMMIT_BEYOND_LOG = 32u
+};
+#define RAFT_AUDIT_ALL 63u
+typedef struct raft_audit_hit {   /* 24 B */
+  uint64_t group;      /* global id: config.group_base + local */
+  uint32_t local;
+  uint8_t  violated;   /* mask of the requested checks this group violates */
+  uint8_t  fault;      /* enum raft_fault (frozen groups are audited like any other) */
+  uint8_t  a, b;       /* witness replicas of the lowest violated check; b = 0xFF where the check names one replica */
+  int32_t  index;      /* witness index (TWO_LEADERS: the shared term) */
+  uint32_t check;      /* the lowest violated check's bit */
+} raft_audit_hit;
+typedef struct raft_audit_info {  /* 88 B */
+  uint64_t matched, written, next_group;
+  uint64_t per_check[8];          /* groups in range violating check bit k; [6], [7] are 0 */
+} raft_audit_info;
+int raft_group_audit(raft_engine* e, uint32_t checks, uint64_t first_group, raft_audit_hit* out, uint64_t cap,
+                     raft_audit_info* info);
+
 /* ---- multi-GPU statistics (RCCL over xGMI) -------------------------------
  * Groups shard by id (config.group_base); the only collective is the sum of
  * tick statistics. raft_tick reduces per-tick records on the device (NSTAT

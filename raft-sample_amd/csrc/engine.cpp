@@ -309,6 +309,9 @@ struct raft_engine {
   // RAFTSTEP_FEED_TIME=1 (read by raft_feed_open): one stderr line per poll with the spans between HIP events
   // around its launches (count + scan + totals, emit, the copy out); costs a synchronise per poll
   hipEvent_t feed_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // group audit (raft_group_audit; k_audit.hip): its scratch, 8 B per group, from the first audit to the
+  // engine's end; an engine that never audits allocates nothing
+  void* audit_rec = nullptr;
   int nranks = 1, rank = 0;
   uint64_t allreduces = 0;      // ncclAllReduce calls issued (diagnostics)
   bool comm_side = false;       // a sum on comm_stream the engine stream has not waited for
@@ -870,6 +873,7 @@ int raft_engine_destroy(raft_engine* e) {
   if (e->list_stream) (void)hipStreamDestroy(e->list_stream);
   if (e->half_stream) (void)hipStreamDestroy(e->half_stream);
   feed_release(e);
+  if (e->audit_rec) (void)hipFree(e->audit_rec);
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->hist) (void)hipFree(e->hist);
   if (e->tstat) (void)hipFree(e->tstat);
@@ -998,11 +1002,30 @@ int gather_view(raft_engine* e, uint64_t first, const uint32_t* ids, uint64_t n,
   if (ids) HIPCHK(hipMemcpyAsync(d_ids, ids, size_t(n) * 4, hipMemcpyHostToDevice, e->stream));
   if (d_bad) HIPCHK(hipMemsetAsync(d_bad, 0, 4, e->stream));
   const int raft = e->cfg.semantics == RAFT_SEM_RAFT;
+  // RAFTSTEP_GROUPS_TIME=1: one stderr line per gather with the summed spans between HIP events around each
+  // chunk's kernels (tools/audit_probe.py: the gather kernels' time inside raft_store_state)
+  const char* gt = getenv("RAFTSTEP_GROUPS_TIME");
+  struct EvList {
+    std::vector<hipEvent_t> v;
+    ~EvList() {
+      for (hipEvent_t x : v) (void)hipEventDestroy(x);
+    }
+  } evs;
+  const bool timed = gt && atoi(gt) > 0;
   for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
     const uint64_t nc = std::min<uint64_t>(chunk, n - c0);
+    if (timed) {
+      for (int k = 0; k < 2; ++k) {
+        hipEvent_t x = nullptr;
+        HIPCHK(hipEventCreate(&x));
+        evs.v.push_back(x);
+      }
+      HIPCHK(hipEventRecord(evs.v[evs.v.size() - 2], e->stream));
+    }
     // (the stream orders this chunk's kernels after the last chunk's copies out of the same buffers)
     HIPCHK(launch_gather(e->R, e->P, raft, uint32_t(first + c0), ids ? d_ids + c0 : nullptr, uint32_t(nc), o, d_bad,
                          e->stream));
+    if (timed) HIPCHK(hipEventRecord(evs.v.back(), e->stream));
     for (const ViewField& f : fields)
       if (f.slot(h))
         HIPCHK(hipMemcpyAsync(static_cast<char*>(f.slot(h)) + c0 * f.bytes(), f.slot(o), nc * f.bytes(),
@@ -1011,6 +1034,16 @@ int gather_view(raft_engine* e, uint64_t first, const uint32_t* ids, uint64_t n,
   uint32_t bad = 0;
   if (d_bad) HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
+  if (timed) {
+    double us = 0;
+    for (size_t k = 0; k + 1 < evs.v.size(); k += 2) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, evs.v[k], evs.v[k + 1]));
+      us += ms * 1e3;
+    }
+    fprintf(stderr, "gather_view: groups %llu chunks %zu logs %d kernels_us %.1f\n", (unsigned long long)n,
+            evs.v.size() / 2, int(h.log_term || h.log_value || h.log_crc), us);
+  }
   if (bad)   // ~(g R + r) of the lowest mismatch (k_groups.hip gather_log_kernel)
     return fail(RAFT_EINTERNAL, "last-entry term cache of group %llu replica %llu differs from the ring's entry",
                 (unsigned long long)(~bad / R), (unsigned long long)(~bad % R));
@@ -2651,6 +2684,121 @@ int raft_load_groups(raft_engine* e, const uint64_t* groups, uint64_t n, const r
   if (int rc = ring_flush(e)) return rc;
   host_mutation(e);
   return scatter_view(e, 0, ids.data(), n, v);
+}
+
+// ---- group audit -----------------------------------------------------------
+// The scan's route to the kernels (directory_read_begin; blocks sums, their
+// scan, the totals and the hits in raft_engine::stage), with two passes in
+// front that leave every group's violated checks and witness in the audit's
+// own scratch (raft_engine::audit_rec; k_audit.hip). Read-only for the state.
+int raft_group_audit(raft_engine* e, uint32_t checks, uint64_t first_group, raft_audit_hit* out, uint64_t cap,
+                     raft_audit_info* info) {
+  static_assert(sizeof(raft_audit_hit) == 24 && sizeof(raft_audit_info) == 88, "raft_audit_hit is 24 B, the info 88 B");
+  if (!e || !info) return fail(RAFT_EINVAL, "null argument");
+  if (!checks || (checks & ~uint32_t(RAFT_AUDIT_ALL)))
+    return fail(RAFT_EINVAL, "raft_group_audit: checks %#x is no set of raft_audit_check bits", checks);
+  if (cap && !out) return fail(RAFT_EINVAL, "raft_group_audit: cap %llu without a buffer", (unsigned long long)cap);
+  const uint64_t G = e->cfg.groups;
+  if (first_group > G)
+    return fail(RAFT_ERANGE, "raft_group_audit: first_group %llu past the engine's %llu groups",
+                (unsigned long long)first_group, (unsigned long long)G);
+  if (int rc = directory_read_begin(e)) return rc;
+  *info = raft_audit_info{};
+  info->next_group = G;
+  if (first_group == G) return RAFT_OK;
+  if (!e->audit_rec) {
+    hipError_t rc = hipMalloc(&e->audit_rec, size_t(G) * 8);
+    if (rc != hipSuccess) {
+      e->audit_rec = nullptr;
+      return fail(RAFT_ENOMEM, "raft_group_audit: %llu bytes of scratch: %s", (unsigned long long)(G * 8),
+                  hipGetErrorString(rc));
+    }
+    e->device_bytes += G * 8;
+  }
+  const uint32_t first = uint32_t(first_group);
+  const uint32_t nb = uint32_t((G + 255) / 256) - (first >> 8);
+  const int raft = e->cfg.semantics == RAFT_SEM_RAFT;
+  const bool logs = checks & (RAFT_AUDIT_LOG_MATCHING | RAFT_AUDIT_COMMIT_DIVERGED | RAFT_AUDIT_TERM_ORDER |
+                              RAFT_AUDIT_STAMP);
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t b_sum = al(size_t(nb) * 4), b_off = al(size_t(nb) * 8), b_tot = 256;
+  const size_t fixed = b_sum + b_off + b_tot;
+  // sixteen words: [0, 4) feed_scan_kernel's accumulators (unused here, zero), [4, 7) its results, [7] next_group,
+  // [8, 14) the groups violating each check
+  unsigned long long res[16] = {};
+  uint64_t room = std::min<uint64_t>(cap, 1u << 16);
+  if (int rc = ensure_stage(e, fixed + size_t(room) * sizeof(raft_audit_hit))) return rc;
+  // RAFTSTEP_AUDIT_TIME=1: one stderr line per audit with the spans between HIP events around its launches
+  // (tools/audit_probe.py; the events cost their creation and a synchronise per call)
+  const char* at_env = getenv("RAFTSTEP_AUDIT_TIME");
+  hipEvent_t tev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  struct EvGuard {
+    hipEvent_t* v;
+    ~EvGuard() {
+      for (int i = 0; i < 6; ++i)
+        if (v[i]) (void)hipEventDestroy(v[i]);
+    }
+  } ev_guard{tev};
+  if (at_env && atoi(at_env) > 0)
+    for (hipEvent_t& x : tev) HIPCHK(hipEventCreate(&x));
+  {
+    char* base = static_cast<char*>(e->stage);
+    uint32_t* bsum = reinterpret_cast<uint32_t*>(base);
+    uint64_t* boff = reinterpret_cast<uint64_t*>(base + b_sum);
+    unsigned long long* tot = reinterpret_cast<unsigned long long*>(base + b_sum + b_off);
+    HIPCHK(hipMemsetAsync(tot, 0, 128, e->stream));
+    if (tev[0]) HIPCHK(hipEventRecord(tev[0], e->stream));
+    HIPCHK(launch_audit_scalar(e->R, e->P, checks, first, e->audit_rec, e->stream));
+    if (tev[0]) HIPCHK(hipEventRecord(tev[1], e->stream));
+    if (logs) HIPCHK(launch_audit_log(e->R, e->P, raft, checks, first, e->audit_rec, e->stream));
+    if (tev[0]) HIPCHK(hipEventRecord(tev[2], e->stream));
+    HIPCHK(launch_audit_count(e->P, first, e->audit_rec, bsum, tot, e->stream));
+    HIPCHK(launch_feed_scan(bsum, boff, nb, tot, tot + 4, e->stream));
+    if (tev[0]) HIPCHK(hipEventRecord(tev[3], e->stream));
+    HIPCHK(hipMemcpyAsync(res, tot, sizeof res, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));   // the total sizes the emit pass and the copy
+  }
+  const uint64_t matched = res[4], n = std::min<uint64_t>(cap, matched);
+  uint64_t next = n == matched ? G : first_group;
+  if (n) {
+    // (a grown buffer: the block offsets are scanned again into it; the records in the scratch stand)
+    if (n > room) {
+      if (int rc = ensure_stage(e, fixed + size_t(n) * sizeof(raft_audit_hit))) return rc;
+      char* base = static_cast<char*>(e->stage);
+      unsigned long long* tot = reinterpret_cast<unsigned long long*>(base + b_sum + b_off);
+      HIPCHK(hipMemsetAsync(tot, 0, 128, e->stream));
+      HIPCHK(launch_audit_count(e->P, first, e->audit_rec, reinterpret_cast<uint32_t*>(base), tot, e->stream));
+      HIPCHK(launch_feed_scan(reinterpret_cast<uint32_t*>(base), reinterpret_cast<uint64_t*>(base + b_sum), nb, tot,
+                              tot + 4, e->stream));
+    }
+    char* base = static_cast<char*>(e->stage);
+    uint64_t* boff = reinterpret_cast<uint64_t*>(base + b_sum);
+    unsigned long long* d_next = reinterpret_cast<unsigned long long*>(base + b_sum + b_off) + 7;
+    void* hits = base + fixed;
+    unsigned long long h_next = 0;
+    if (tev[0]) HIPCHK(hipEventRecord(tev[4], e->stream));
+    HIPCHK(launch_audit_emit(e->P, first, e->audit_rec, boff, n, hits, d_next, e->stream));
+    if (tev[0]) HIPCHK(hipEventRecord(tev[5], e->stream));
+    HIPCHK(hipMemcpyAsync(out, hits, size_t(n) * sizeof(raft_audit_hit), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&h_next, d_next, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (n < matched) next = h_next;
+  }
+  if (tev[0]) {
+    float sc = 0, lg = 0, cs = 0, em = 0;
+    HIPCHK(hipEventElapsedTime(&sc, tev[0], tev[1]));
+    HIPCHK(hipEventElapsedTime(&lg, tev[1], tev[2]));
+    HIPCHK(hipEventElapsedTime(&cs, tev[2], tev[3]));
+    if (n) HIPCHK(hipEventElapsedTime(&em, tev[4], tev[5]));
+    fprintf(stderr, "raft_group_audit: checks %u matched %llu written %llu scalar_us %.1f log_us %.1f count_scan_us %.1f "
+            "emit_us %.1f\n", checks, (unsigned long long)matched, (unsigned long long)n, sc * 1e3, lg * 1e3, cs * 1e3,
+            em * 1e3);
+  }
+  info->matched = matched;
+  info->written = n;
+  info->next_group = next;
+  for (int k = 0; k < 6; ++k) info->per_check[k] = res[8 + k];
+  return RAFT_OK;
 }
 
 }  // extern "C"

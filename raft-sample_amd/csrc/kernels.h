@@ -260,6 +260,25 @@ hipError_t launch_scatter(int R, const DevPlanes& P, int raft, uint32_t first, c
 // be null): the open commit feed's, [G][nm], set to 0 for those groups.
 hipError_t launch_restart(int R, const DevPlanes& P, const Trace& T, const uint32_t* ids, uint32_t n, int32_t* cursors,
                           uint32_t nm, hipStream_t s);
+// Group audit (k_audit.hip; raft_group_audit). checks: enum raft_audit_check;
+// rec: the audit's scratch, 8 B per group of the engine; the launches cover
+// the 256-group blocks from the one holding `first` on, as the scan's do.
+// launch_audit_scalar: every group of [first, G) gets its record (violated
+// checks, the lowest one's witness, the fault code) from the scalar checks,
+// one lane per group. launch_audit_log (after it, when `checks` has a log
+// bit): the log checks, one wave per group, merged into the records.
+// launch_audit_count: per block its hits (bsum), and tot[8 + k] += the groups
+// violating check bit k (tot: 16 words, zero before the launch).
+// launch_audit_emit: hits [0, cap) of the ascending group order to `out`
+// (24 B each, raft_audit_hit), cap >= 1 and at most the total; *next = the
+// local id after hit cap - 1.
+hipError_t launch_audit_scalar(int R, const DevPlanes& P, uint32_t checks, uint32_t first, void* rec, hipStream_t s);
+hipError_t launch_audit_log(int R, const DevPlanes& P, int raft, uint32_t checks, uint32_t first, void* rec,
+                            hipStream_t s);
+hipError_t launch_audit_count(const DevPlanes& P, uint32_t first, const void* rec, uint32_t* bsum,
+                              unsigned long long* tot, hipStream_t s);
+hipError_t launch_audit_emit(const DevPlanes& P, uint32_t first, const void* rec, const uint64_t* boff, uint64_t cap,
+                             void* out, unsigned long long* next, hipStream_t s);
 hipError_t launch_stream_probe(int R, const uint16_t* a, SsRec* b, const uint16_t* c, int32_t* d, int32_t* rt,
                                int64_t* rv, uint32_t n, uint32_t slot, uint32_t kslots, hipStream_t s,
                                uint32_t mode = 0);

@@ -203,6 +203,22 @@ class ScanInfo(C.Structure):
     _fields_ = [("matched", C.c_uint64), ("written", C.c_uint64), ("next_group", C.c_uint64)]
 
 
+# group audit (raft_audit_hit / raft_audit_info / enum raft_audit_check)
+AUDIT_HIT = np.dtype([("group", "<u8"), ("local", "<u4"), ("violated", "u1"), ("fault", "u1"), ("a", "u1"), ("b", "u1"),
+                      ("index", "<i4"), ("check", "<u4")], align=True)
+(AUDIT_TWO_LEADERS, AUDIT_LOG_MATCHING, AUDIT_COMMIT_DIVERGED, AUDIT_TERM_ORDER, AUDIT_STAMP,
+ AUDIT_COMMIT_BEYOND_LOG) = 1, 2, 4, 8, 16, 32
+AUDIT_ALL = 63
+AUDIT_NAMES = ("two_leaders", "log_matching", "commit_diverged", "term_order", "stamp", "commit_beyond_log")
+NO_REPLICA = 0xFF   # raft_audit_hit.b: the check names one replica
+
+
+class AuditInfo(C.Structure):
+    _fields_ = [("matched", C.c_uint64), ("written", C.c_uint64), ("next_group", C.c_uint64),
+                ("per_check", C.c_uint64 * 8)]
+
+
+assert AUDIT_HIT.itemsize == 24 and C.sizeof(AuditInfo) == 88
 assert AE_REQ.itemsize == 64 and AE_RESP.itemsize == 24 and LOG_ENTRY.itemsize == 16
 assert VOTE_REQ.itemsize == 40 and VOTE_RESP.itemsize == 16
 assert GROUP_OP.itemsize == 24 and OP_RESULT.itemsize == 16
@@ -256,15 +272,16 @@ SIGNATURES = {
     "raft_store_groups": (C.c_int, [P, P, C.c_uint64, P]),
     "raft_restart_groups": (C.c_int, [P, P, C.c_uint64, C.c_int64]),
     "raft_load_groups": (C.c_int, [P, P, C.c_uint64, P]),
+    "raft_group_audit": (C.c_int, [P, C.c_uint32, C.c_uint64, P, C.c_uint64, P]),
 }
 
 
 # measurement / diagnostics entry points added in round 5: an older build
 # loaded through RAFTSTEP_LIB (A/B runs) may lack them
-# (and the commit feed and the group directory, added later still)
+# (and the commit feed, the group directory and the group audit, added later still)
 OPTIONAL = ("raft_debug_diag_mode", "raft_stream_probe", "raft_engine_features",
             "raft_feed_open", "raft_feed_poll", "raft_feed_cursors", "raft_feed_close",
-            "raft_group_scan", "raft_store_groups", "raft_restart_groups", "raft_load_groups")
+            "raft_group_scan", "raft_store_groups", "raft_restart_groups", "raft_load_groups", "raft_group_audit")
 FEATURE_SHARED_ENTRIES, FEATURE_VIRTUAL_SUFFIXES = 1, 2   # raft_engine_features (include/raftstep.h)
 PROBE_PLAIN_RING, PROBE_NT_RECORD, PROBE_NO_HEARTBEAT = 1, 2, 4   # raft_stream_probe flags
 

@@ -262,6 +262,24 @@ class Engine:
         v = abi.make_view(rows)
         _check(self.lib.raft_load_groups(self.h, _ptr(ids), len(ids), C.byref(v)))
 
+    # -- group audit ---------------------------------------------------
+    def group_audit(self, checks=abi.AUDIT_ALL, first_group=0, cap=None):
+        """Groups in [first_group, G) that violate one of the safety
+        invariants `checks` names (raft_group_audit; abi.AUDIT_* bits):
+        (AUDIT_HIT array in ascending group order, each with the witness of
+        its lowest violated check; info dict with matched, written, next_group
+        and per_check, the groups violating each check by abi.AUDIT_NAMES).
+        cap=None counts first, then takes every hit."""
+        info = abi.AuditInfo()
+        if cap is None:
+            _check(self.lib.raft_group_audit(self.h, int(checks), int(first_group), None, 0, C.byref(info)))
+            cap = info.matched
+        out = np.zeros(int(cap), abi.AUDIT_HIT)
+        _check(self.lib.raft_group_audit(self.h, int(checks), int(first_group), _ptr(out), int(cap), C.byref(info)))
+        d = dict(matched=int(info.matched), written=int(info.written), next_group=int(info.next_group),
+                 per_check={k: int(info.per_check[i]) for i, k in enumerate(abi.AUDIT_NAMES)})
+        return out[:d["written"]], d
+
     # -- the fused tick ------------------------------------------------
     def tick(self, first_tick, nticks=1, stats=True):
         if stats:

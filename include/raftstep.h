@@ -384,6 +384,108 @@ int raft_feed_poll(raft_engine* e, raft_feed_entry* out, uint64_t cap, raft_feed
 int raft_feed_cursors(raft_engine* e, int32_t* out);
 int raft_feed_close(raft_engine* e);   /* (no open feed: nothing to do) */
 
+/* ---- client proposals -----------------------------------------------------
+ * The way into the log for a caller that owns its own requests: a list of
+ * (group, value) per call, several for hot groups and none for cold ones
+ * (main.go:87-93 sends each LogReq to every node that is Leader), a ticket per
+ * request with the index and term its entry received, and a cheap read-only
+ * question about outstanding tickets (main.go:330: the leader answers the
+ * client once CommitIndex has advanced). The commit feed delivers what was
+ * committed; raft_ticket_status also says that a ticket never will be.
+ *
+ * raft_propose(now_tick, props[0..n), out[0..n)): out[i] is the ticket of
+ * props[i]. Rules:
+ *   Proposals are applied in list order. A group may appear any number of
+ *     times; its k-th proposal sees the state its (k-1)-th left. Different
+ *     groups are independent.
+ *   One proposal for group g:
+ *     g frozen (fault code not 0): RAFT_PROPOSE_FROZEN, nothing appended,
+ *       leader 0xFF, leaders 0.
+ *     Otherwise every replica whose State is Leader, in ascending id, runs
+ *       LogReq (main.go:327-329): exactly what RAFT_OP_CLIENT_APPEND does to
+ *       one replica (the entry's Term = the Leader's Term, the value, with
+ *       payload_crc its stamp; LastApplied + 1; RAFT: the high-water mark).
+ *     An append that would leave int32 (LastApplied == 2^31-1) freezes the
+ *       group with RAFT_F_OVERFLOW at that append: later Leaders of this
+ *       proposal append nothing, nor do later proposals of the group.
+ *     RAFT_PROPOSE_ACCEPTED <=> the lowest-id Leader appended <=> leaders != 0;
+ *       index and term are that Leader's. With leaders == 0 the status is
+ *       RAFT_PROPOSE_FROZEN when the group is frozen after the proposal (the
+ *       lowest-id Leader's append overflowed), RAFT_PROPOSE_NO_LEADER otherwise
+ *       (no replica is Leader).
+ *     fault is the group's code after the proposal in every case (ACCEPTED
+ *       with fault 5: a higher-id Leader's append overflowed).
+ *   n = 0 changes nothing, and the steady tick's forms stay.
+ *   Every argument error is found before anything is written: a NULL argument
+ *     (with n > 0) or n > 2^31 is RAFT_EINVAL, an id >= G is RAFT_ERANGE, a
+ *     now_tick that is negative or leaves int32 seconds is RAFT_ERANGE.
+ *   A poisoned engine answers RAFT_EINTERNAL.
+ *   Allowed with any client_source and any client_period (the proposals are in
+ *     addition to whatever the ticks append).
+ *   The call takes the handler batches' route: like one, it ends the steady
+ *     tick's list skip and steady form until the next raft_init_steady. An
+ *     open feed stays open and no cursor moves: logs only grow. */
+typedef struct raft_proposal { uint64_t group; int64_t value; } raft_proposal;   /* 16 B; group = local id */
+enum raft_propose_status { RAFT_PROPOSE_NONE = 0, RAFT_PROPOSE_ACCEPTED = 1,
+                           RAFT_PROPOSE_NO_LEADER = 2, RAFT_PROPOSE_FROZEN = 3 };
+typedef struct raft_ticket {          /* 32 B */
+  uint64_t group;    /* global id: config.group_base + local */
+  int64_t  value;    /* the proposal's value, echoed */
+  uint32_t local;
+  int32_t  index;    /* 1-based log index the entry got at the lowest-id Leader; 0 unless ACCEPTED */
+  int32_t  term;     /* that Leader's Term = the entry's Log.Term; 0 unless ACCEPTED */
+  uint8_t  status;   /* enum raft_propose_status */
+  uint8_t  leader;   /* the lowest-id replica that appended, 0xFF: none */
+  uint8_t  leaders;  /* mask of the replicas that appended (main.go:90-93 sends to every Leader) */
+  uint8_t  fault;    /* the group's fault code after this proposal */
+} raft_ticket;
+int raft_propose(raft_engine* e, int64_t now_tick, const raft_proposal* props, uint64_t n, raft_ticket* out);
+/* raft_ticket_status(tickets[0..n), out, info): read-only and stateless, on
+ * the canonical view; K, top_r, lo_r, "live" and entry equality are the group
+ * audit's (below). Rules:
+ *   A ticket with status != RAFT_PROPOSE_ACCEPTED or index <= 0 is
+ *     RAFT_TICKET_INVALID: replica 0xFF, masks 0 (raft_propose's output can be
+ *     passed back as it is).
+ *   Otherwise replica r (l = last_r, cm = commit_r) is
+ *     absent   when index > l;
+ *     gone     when index <= l and index < lo_r (the entry has left the ring);
+ *     same or other when the entry is live (lo_r <= index <= l), by comparing
+ *              its Term and Value with the ticket's;
+ *     decided  when index <= min(cm, l).
+ *   The result is the first of these that applies:
+ *     1. some replica is decided and live: the lowest-id such replica is the
+ *        witness; RAFT_TICKET_COMMITTED if it is same, else _SUPERSEDED;
+ *     2. some replica is decided and gone: RAFT_TICKET_EVICTED, 0xFF (the
+ *        outcome can no longer be read from the rings);
+ *     3. some replica is same: RAFT_TICKET_PENDING, the lowest-id holder;
+ *     4. some replica is gone: RAFT_TICKET_EVICTED, 0xFF;
+ *     5. RAFT_TICKET_DROPPED, 0xFF: no replica holds the entry and no
+ *        committed prefix reaches an entry that is still readable. Final.
+ *   holders and committed are filled in every state but INVALID; fault is the
+ *     group's code now in every state.
+ *   info->per_state[k] = the tickets in state k. Tickets come in any order,
+ *     repeats allowed. out may be NULL (only counts); info may be NULL when
+ *     out is not; both NULL with n > 0, NULL tickets with n > 0 or n > 2^31 is
+ *     RAFT_EINVAL. local >= G is RAFT_ERANGE; group != group_base + local is
+ *     RAFT_EINVAL (another shard's ticket); nothing is written in either case.
+ *   The call reads as raft_group_scan does: no group leaves its shared form,
+ *     the steady tick's forms stay, the feed is left alone, frozen groups are
+ *     read like any other. The same state and tickets give the same bytes. A
+ *     poisoned engine answers RAFT_EINTERNAL. */
+enum raft_ticket_state { RAFT_TICKET_COMMITTED = 0, RAFT_TICKET_SUPERSEDED = 1, RAFT_TICKET_PENDING = 2,
+                         RAFT_TICKET_EVICTED = 3, RAFT_TICKET_DROPPED = 4, RAFT_TICKET_INVALID = 5 };
+typedef struct raft_ticket_result {   /* 8 B */
+  uint8_t state;      /* enum raft_ticket_state */
+  uint8_t replica;    /* witness, 0xFF where the state names none */
+  uint8_t fault;      /* the group's fault code now */
+  uint8_t holders;    /* mask: replicas whose live entry at index equals (term, value) */
+  uint8_t committed;  /* mask: holders with index <= min(CommitIndex, LastApplied) */
+  uint8_t reserved[3];/* 0 */
+} raft_ticket_result;
+typedef struct raft_ticket_info { uint64_t per_state[8]; } raft_ticket_info;  /* [6], [7] are 0 */
+int raft_ticket_status(raft_engine* e, const raft_ticket* tickets, uint64_t n, raft_ticket_result* out,
+                       raft_ticket_info* info);
+
 /* ---- group directory ------------------------------------------------------
  * The way out of the fault codes, and the way back in: find groups by what is
  * wrong with them, read the canonical view of a list of groups, and restart

@@ -24,6 +24,7 @@
 
 #include "../../include/raftstep.h"
 #include "kernels.h"
+#include "propose_plan.hpp"
 
 using namespace raftstep;
 
@@ -2798,6 +2799,95 @@ int raft_group_audit(raft_engine* e, uint32_t checks, uint64_t first_group, raft
   info->written = n;
   info->next_group = next;
   for (int k = 0; k < 6; ++k) info->per_check[k] = res[8 + k];
+  return RAFT_OK;
+}
+
+// ---- client proposals ------------------------------------------------------
+// raft_propose: the handler batches' route (settle_check, ring_flush,
+// host_mutation) for their reasons: the leaders' logs leave the trace's run
+// and the compressed steady state the list skip and the steady form are proven
+// for. The list is planned on the host (propose_plan.hpp: list positions by
+// group, segment starts, the range check) and uploaded with the plan into
+// raft_engine::stage; one launch, one lane per distinct group. Every argument
+// error is found before anything is written.
+int raft_propose(raft_engine* e, int64_t now_tick, const raft_proposal* props, uint64_t n, raft_ticket* out) {
+  static_assert(sizeof(raft_proposal) == 16 && sizeof(raft_ticket) == 32 && sizeof(DevProposal) == sizeof(raft_proposal),
+                "raft_proposal is 16 B, raft_ticket 32 B");
+  if (!e || (n && (!props || !out))) return fail(RAFT_EINVAL, "null argument");
+  ProposePlan plan;
+  uint64_t bad = 0;
+  switch (propose_plan(props, sizeof(raft_proposal), n, e->cfg.groups, &plan, &bad)) {
+    case PLAN_TOO_LONG:
+      return fail(RAFT_EINVAL, "raft_propose: %llu proposals, at most 2^31 per call", (unsigned long long)n);
+    case PLAN_RANGE:
+      return fail(RAFT_ERANGE, "raft_propose: element %llu: group %llu outside the engine's %llu",
+                  (unsigned long long)bad, (unsigned long long)props[bad].group, (unsigned long long)e->cfg.groups);
+    default:
+      break;
+  }
+  if (int rc = check_ticks(e, now_tick, 1)) return rc;
+  if (int rc = settle_check(e)) return rc;
+  if (!n) return RAFT_OK;
+  const uint32_t nseg = plan.segments();
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t b_props = al(size_t(n) * sizeof(raft_proposal)), b_perm = al(size_t(n) * 4),
+               b_seg = al((size_t(nseg) + 1) * 4), b_out = al(size_t(n) * sizeof(raft_ticket));
+  if (int rc = ensure_stage(e, b_props + b_perm + b_seg + b_out)) return rc;
+  if (int rc = ring_flush(e)) return rc;
+  host_mutation(e);
+  HIPCHK(hipSetDevice(e->cfg.device));
+  char* base = static_cast<char*>(e->stage);
+  DevProposal* d_props = reinterpret_cast<DevProposal*>(base);
+  uint32_t* d_perm = reinterpret_cast<uint32_t*>(base + b_props);
+  uint32_t* d_seg = reinterpret_cast<uint32_t*>(base + b_props + b_perm);
+  void* d_out = base + b_props + b_perm + b_seg;
+  HIPCHK(hipMemcpyAsync(d_props, props, size_t(n) * sizeof(raft_proposal), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_perm, plan.perm.data(), size_t(n) * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_seg, plan.seg.data(), (size_t(nseg) + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(launch_propose(e->R, int(e->cfg.semantics), e->P, make_trace(e, now_tick), d_props, d_perm, d_seg, nseg, d_out,
+                        e->stream));
+  HIPCHK(hipMemcpyAsync(out, d_out, size_t(n) * sizeof(raft_ticket), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return RAFT_OK;
+}
+
+// raft_ticket_status: the scan's route (directory_read_begin), read-only. The
+// tickets are checked on the host (every local id inside the engine, every
+// global id this shard's) before anything is written, then staged with the
+// results and the eight state counters in raft_engine::stage.
+int raft_ticket_status(raft_engine* e, const raft_ticket* tickets, uint64_t n, raft_ticket_result* out,
+                       raft_ticket_info* info) {
+  static_assert(sizeof(raft_ticket_result) == 8 && sizeof(raft_ticket_info) == 64,
+                "raft_ticket_result is 8 B, raft_ticket_info 64 B");
+  if (!e || (n && (!tickets || (!out && !info)))) return fail(RAFT_EINVAL, "null argument");
+  if (n > PROPOSE_MAX)
+    return fail(RAFT_EINVAL, "raft_ticket_status: %llu tickets, at most 2^31 per call", (unsigned long long)n);
+  const uint64_t G = e->cfg.groups, gbase = e->cfg.group_base;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (tickets[i].local >= G)
+      return fail(RAFT_ERANGE, "raft_ticket_status: ticket %llu: group %u outside the engine's %llu",
+                  (unsigned long long)i, tickets[i].local, (unsigned long long)G);
+    if (tickets[i].group != gbase + tickets[i].local)
+      return fail(RAFT_EINVAL, "raft_ticket_status: ticket %llu: global id %llu is not this shard's group %u",
+                  (unsigned long long)i, (unsigned long long)tickets[i].group, tickets[i].local);
+  }
+  if (int rc = directory_read_begin(e)) return rc;
+  if (info) *info = raft_ticket_info{};
+  if (!n) return RAFT_OK;
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t b_tot = 256, b_tk = al(size_t(n) * sizeof(raft_ticket)), b_out = out ? al(size_t(n) * 8) : 0;
+  if (int rc = ensure_stage(e, b_tot + b_tk + b_out)) return rc;
+  char* base = static_cast<char*>(e->stage);
+  unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(base);
+  void* d_tk = base + b_tot;
+  void* d_out = out ? base + b_tot + b_tk : nullptr;
+  if (info) HIPCHK(hipMemsetAsync(d_tot, 0, 64, e->stream));
+  HIPCHK(hipMemcpyAsync(d_tk, tickets, size_t(n) * sizeof(raft_ticket), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(launch_ticket_status(e->R, e->P, e->cfg.semantics == RAFT_SEM_RAFT, d_tk, uint32_t(n), d_out,
+                              info ? d_tot : nullptr, e->stream));
+  if (out) HIPCHK(hipMemcpyAsync(out, d_out, size_t(n) * 8, hipMemcpyDeviceToHost, e->stream));
+  if (info) HIPCHK(hipMemcpyAsync(info->per_state, d_tot, 64, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
   return RAFT_OK;
 }
 

@@ -272,6 +272,10 @@ hipError_t launch_ops_ref(int R, const DevPlanes& P, const Trace& T, const DevOp
                           const int64_t* ev, const uint32_t* ec, DevRes* out, hipStream_t s);
 hipError_t launch_ops_raft(int R, const DevPlanes& P, const Trace& T, const DevOp* ops, uint32_t n, const int32_t* et,
                            const int64_t* ev, const uint32_t* ec, DevRes* out, hipStream_t s);
+hipError_t launch_propose_ref(int R, const DevPlanes& P, const Trace& T, const DevProposal* props, const uint32_t* perm,
+                              const uint32_t* seg, uint32_t nseg, void* out, hipStream_t s);
+hipError_t launch_propose_raft(int R, const DevPlanes& P, const Trace& T, const DevProposal* props, const uint32_t* perm,
+                               const uint32_t* seg, uint32_t nseg, void* out, hipStream_t s);
 
 hipError_t launch_tick_slow(int R, int sem, const DevPlanes& P, const Trace& T0, int64_t first_tick, int64_t win_first, int64_t last_tick,
                             unsigned long long* stats, const uint32_t* work, const int32_t* work_tick,
@@ -286,6 +290,11 @@ hipError_t launch_ops(int R, int sem, const DevPlanes& P, const Trace& T, const 
                       const int32_t* et, const int64_t* ev, const uint32_t* ec, DevRes* out, hipStream_t s) {
   return sem == SEM_RAFT ? launch_ops_raft(R, P, T, ops, n, et, ev, ec, out, s)
                          : launch_ops_ref(R, P, T, ops, n, et, ev, ec, out, s);
+}
+hipError_t launch_propose(int R, int sem, const DevPlanes& P, const Trace& T, const DevProposal* props,
+                          const uint32_t* perm, const uint32_t* seg, uint32_t nseg, void* out, hipStream_t s) {
+  return sem == SEM_RAFT ? launch_propose_raft(R, P, T, props, perm, seg, nseg, out, s)
+                         : launch_propose_ref(R, P, T, props, perm, seg, nseg, out, s);
 }
 hipError_t launch_init_new(int R, const DevPlanes& P, const Trace& T, hipStream_t s) {
   RAFT_DISPATCH_R(R, hipLaunchKernelGGL(init_new_kernel<RR>, grid_for(P.G), dim3(256), 0, s, P, T));

@@ -13,5 +13,9 @@ hipError_t launch_ops_ref(int R, const DevPlanes& P, const Trace& T, const DevOp
                           const int64_t* ev, const uint32_t* ec, DevRes* out, hipStream_t s) {
   return launch_ops_sem<SEM_REF>(R, P, T, ops, n, et, ev, ec, out, s);
 }
+hipError_t launch_propose_ref(int R, const DevPlanes& P, const Trace& T, const DevProposal* props, const uint32_t* perm,
+                              const uint32_t* seg, uint32_t nseg, void* out, hipStream_t s) {
+  return launch_propose_sem<SEM_REF>(R, P, T, props, perm, seg, nseg, out, s);
+}
 
 }  // namespace raftstep

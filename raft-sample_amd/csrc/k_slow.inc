@@ -244,6 +244,56 @@ __global__ __launch_bounds__(256) void ops_kernel(DevPlanes P, Trace T, const De
   out[i] = res;
 }
 
+// raft_propose: one lane per distinct group of the batch. Lane i owns the
+// list positions perm[seg[i] .. seg[i + 1]) (the host's plan, propose_plan.hpp:
+// all of one group, in list order) and runs each proposal's LogReq
+// (main.go:327-329) on every replica whose State is Leader, in ascending id,
+// through client_append_value: what OP_CLIENT_APPEND does to one replica. The
+// group is loaded once and stored once; a proposal sees the state the one
+// before it left, a fault (F_OVERFLOW at LastApplied 2^31-1) included. Each
+// 32-B raft_ticket goes to its own list position as two 16-B stores.
+template <int R, int SEM>
+__global__ __launch_bounds__(256) void propose_kernel(DevPlanes P, Trace T, const DevProposal* props, const uint32_t* perm,
+                                                      const uint32_t* seg, uint32_t nseg, uint4* out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= nseg) return;
+  const uint32_t b = seg[i], e = seg[i + 1];
+  const uint32_t g = uint32_t(props[perm[b]].group);
+  const uint64_t gid = P.gbase + g;
+  __shared__ int glds[group_lds_ints<R>() * 256];
+  Group<R, SEM> G;
+  G.bind(glds);
+  G.begin(P, T, g);
+  const bool loaded = !G.fault;
+  if (loaded) G.load(P, false);
+  for (uint32_t j = b; j < e; ++j) {
+    const uint32_t pos = perm[j];
+    const int64_t v = props[pos].value;
+    uint32_t leaders = 0, leader = 0xFFu;
+    int index = 0, term = 0;
+    if (!G.fault) {
+#pragma unroll 1
+      for (int r = 0; r < R; ++r) {
+        if (G.role(r) != ROLE_L) continue;
+        G.client_append_value(P, r, v);
+        if (G.fault) break;   // (frozen at this append: later leaders append nothing)
+        if (!leaders) {
+          leader = uint32_t(r);
+          index = sel(G.last, r);
+          term = sel(G.term, r);
+        }
+        leaders |= 1u << r;
+      }
+    }
+    // RAFT_PROPOSE_ACCEPTED = 1, _NO_LEADER = 2, _FROZEN = 3
+    const uint32_t status = leaders ? 1u : (G.fault ? 3u : 2u);
+    const uint32_t w = status | (leader << 8) | (leaders << 16) | (uint32_t(G.fault) << 24);
+    out[size_t(pos) * 2u] = uint4{uint32_t(gid), uint32_t(gid >> 32), uint32_t(uint64_t(v)), uint32_t(uint64_t(v) >> 32)};
+    out[size_t(pos) * 2u + 1u] = uint4{g, uint32_t(index), uint32_t(term), w};
+  }
+  if (loaded) G.store(P, uint32_t(T.entries_before(T.tick + 1)));
+}
+
 // One resident wave of blocks (resident_blocks, tick_common.hpp) grid-striding
 // over the worklist: an empty worklist costs one short wave of blocks, a long
 // one has no partial block-round tail.
@@ -276,6 +326,13 @@ hipError_t launch_ops_sem(int R, const DevPlanes& P, const Trace& T, const DevOp
                           const int64_t* ev, const uint32_t* ec, DevRes* out, hipStream_t s) {
   RAFT_DISPATCH_R(R, hipLaunchKernelGGL((ops_kernel<RR, SEM>), grid_for(n), dim3(256), 0, s, P, T, ops, n, et, ev,
                                         ec, out));
+  return hipGetLastError();
+}
+template <int SEM>
+hipError_t launch_propose_sem(int R, const DevPlanes& P, const Trace& T, const DevProposal* props, const uint32_t* perm,
+                              const uint32_t* seg, uint32_t nseg, void* out, hipStream_t s) {
+  RAFT_DISPATCH_R(R, hipLaunchKernelGGL((propose_kernel<RR, SEM>), grid_for(nseg), dim3(256), 0, s, P, T, props, perm,
+                                        seg, nseg, static_cast<uint4*>(out)));
   return hipGetLastError();
 }
 

@@ -135,6 +135,23 @@ hipError_t launch_tick_slow(int R, int sem, const DevPlanes& P, const Trace& T0,
                             const uint32_t* work_count, uint32_t* next_count, int lane_per_group, hipStream_t s);
 hipError_t launch_ops(int R, int sem, const DevPlanes& P, const Trace& T, const DevOp* ops, uint32_t n,
                       const int32_t* et, const int64_t* ev, const uint32_t* ec, DevRes* out, hipStream_t s);
+// Client proposals (raft_propose; propose_kernel<R,SEM>, k_ref.hip /
+// k_raft.hip). props: the call's raft_proposal list as it came, ids range-
+// checked by the host; perm / seg: the plan of propose_plan.hpp (list
+// positions by group, nseg + 1 segment starts); out: 32 B per proposal
+// (raft_ticket), indexed by list position, 16-B aligned.
+struct DevProposal {
+  uint64_t group;
+  int64_t value;
+};
+hipError_t launch_propose(int R, int sem, const DevPlanes& P, const Trace& T, const DevProposal* props,
+                          const uint32_t* perm, const uint32_t* seg, uint32_t nseg, void* out, hipStream_t s);
+// raft_ticket_status (ticket_status_kernel<R>, k_propose.hip): one lane per
+// ticket of tickets[0..n) (32 B each, checked by the host: local < G), read on
+// the canonical view. out (may be null): 8 B per ticket (raft_ticket_result);
+// tot (may be null): 8 words, tot[k] += the tickets in state k.
+hipError_t launch_ticket_status(int R, const DevPlanes& P, int raft, const void* tickets, uint32_t n, void* out,
+                                unsigned long long* tot, hipStream_t s);
 hipError_t launch_init_new(int R, const DevPlanes& P, const Trace& T, hipStream_t s);
 // Per-group state digest (same definition as oracle_state_digest) + wrapping sum.
 hipError_t launch_digest(int R, const DevPlanes& P, int raft, uint64_t* per_group, unsigned long long* total,

@@ -218,6 +218,23 @@ class AuditInfo(C.Structure):
                 ("per_check", C.c_uint64 * 8)]
 
 
+# client proposals (raft_proposal / raft_ticket / raft_ticket_result / raft_ticket_info)
+PROPOSAL = np.dtype([("group", "<u8"), ("value", "<i8")], align=True)
+TICKET = np.dtype([("group", "<u8"), ("value", "<i8"), ("local", "<u4"), ("index", "<i4"), ("term", "<i4"),
+                   ("status", "u1"), ("leader", "u1"), ("leaders", "u1"), ("fault", "u1")], align=True)
+TICKET_RESULT = np.dtype([("state", "u1"), ("replica", "u1"), ("fault", "u1"), ("holders", "u1"), ("committed", "u1"),
+                          ("reserved", "u1", (3,))], align=True)
+PROPOSE_NONE, PROPOSE_ACCEPTED, PROPOSE_NO_LEADER, PROPOSE_FROZEN = range(4)   # enum raft_propose_status
+(TICKET_COMMITTED, TICKET_SUPERSEDED, TICKET_PENDING, TICKET_EVICTED, TICKET_DROPPED,
+ TICKET_INVALID) = range(6)                                                    # enum raft_ticket_state
+TICKET_STATE_NAMES = ("committed", "superseded", "pending", "evicted", "dropped", "invalid")
+
+
+class TicketInfo(C.Structure):
+    _fields_ = [("per_state", C.c_uint64 * 8)]
+
+
+assert PROPOSAL.itemsize == 16 and TICKET.itemsize == 32 and TICKET_RESULT.itemsize == 8 and C.sizeof(TicketInfo) == 64
 assert AUDIT_HIT.itemsize == 24 and C.sizeof(AuditInfo) == 88
 assert AE_REQ.itemsize == 64 and AE_RESP.itemsize == 24 and LOG_ENTRY.itemsize == 16
 assert VOTE_REQ.itemsize == 40 and VOTE_RESP.itemsize == 16
@@ -273,15 +290,18 @@ SIGNATURES = {
     "raft_restart_groups": (C.c_int, [P, P, C.c_uint64, C.c_int64]),
     "raft_load_groups": (C.c_int, [P, P, C.c_uint64, P]),
     "raft_group_audit": (C.c_int, [P, C.c_uint32, C.c_uint64, P, C.c_uint64, P]),
+    "raft_propose": (C.c_int, [P, C.c_int64, P, C.c_uint64, P]),
+    "raft_ticket_status": (C.c_int, [P, P, C.c_uint64, P, P]),
 }
 
 
 # measurement / diagnostics entry points added in round 5: an older build
 # loaded through RAFTSTEP_LIB (A/B runs) may lack them
-# (and the commit feed, the group directory and the group audit, added later still)
+# (and the commit feed, the group directory, the group audit and the client proposals, added later still)
 OPTIONAL = ("raft_debug_diag_mode", "raft_stream_probe", "raft_engine_features",
             "raft_feed_open", "raft_feed_poll", "raft_feed_cursors", "raft_feed_close",
-            "raft_group_scan", "raft_store_groups", "raft_restart_groups", "raft_load_groups", "raft_group_audit")
+            "raft_group_scan", "raft_store_groups", "raft_restart_groups", "raft_load_groups", "raft_group_audit",
+            "raft_propose", "raft_ticket_status")
 FEATURE_SHARED_ENTRIES, FEATURE_VIRTUAL_SUFFIXES = 1, 2   # raft_engine_features (include/raftstep.h)
 PROBE_PLAIN_RING, PROBE_NT_RECORD, PROBE_NO_HEARTBEAT = 1, 2, 4   # raft_stream_probe flags
 

@@ -280,6 +280,32 @@ class Engine:
                  per_check={k: int(info.per_check[i]) for i, k in enumerate(abi.AUDIT_NAMES)})
         return out[:d["written"]], d
 
+    # -- client proposals ----------------------------------------------
+    def propose(self, now_tick, groups, values):
+        """Append values[i] to the log of every Leader of groups[i] (local ids,
+        any order, repeats allowed; applied in list order) at virtual tick
+        now_tick (raft_propose): the TICKET array, one per proposal."""
+        ids = self._ids(groups)
+        vals = np.asarray(values)
+        if vals.shape != ids.shape or (vals.size and vals.dtype.kind not in "iu"):
+            raise ValueError("proposal values: one integer per group id expected")
+        props = np.zeros(len(ids), abi.PROPOSAL)
+        props["group"] = ids
+        props["value"] = vals.astype(np.int64)
+        out = np.zeros(len(ids), abi.TICKET)
+        _check(self.lib.raft_propose(self.h, int(now_tick), _ptr(props), len(props), _ptr(out)))
+        return out
+
+    def ticket_status(self, tickets, results=True):
+        """What became of each ticket (raft_ticket_status; read-only):
+        (TICKET_RESULT array, or None with results=False, which only counts;
+        {state name: tickets} by abi.TICKET_STATE_NAMES)."""
+        tickets = np.ascontiguousarray(tickets, dtype=abi.TICKET)
+        info = abi.TicketInfo()
+        out = np.zeros(len(tickets), abi.TICKET_RESULT) if results else None
+        _check(self.lib.raft_ticket_status(self.h, _ptr(tickets), len(tickets), _ptr(out), C.byref(info)))
+        return out, {k: int(info.per_state[i]) for i, k in enumerate(abi.TICKET_STATE_NAMES)}
+
     # -- the fused tick ------------------------------------------------
     def tick(self, first_tick, nticks=1, stats=True):
         if stats:

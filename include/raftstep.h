@@ -162,7 +162,12 @@ typedef struct raft_state_view {
   int32_t* last;      /* Node.LastApplied == len(Node.Log) (main.go:25, 148-149, 328-329) */
   int32_t* commit;    /* Node.CommitIndex (main.go:24) */
   int32_t* deadline;  /* election timer deadline, virtual seconds */
-  int32_t* timeout;   /* current timer duration d, seconds (main.go:114, 194) */
+  int32_t* timeout;   /* current timer duration d, seconds (main.go:114, 194). A load accepts 0..1023 (the
+                       * 10-bit duration field; the configured ranges end at min + span <= 1024) and
+                       * refuses anything else with RAFT_EINVAL. 0, which no configured range draws, is a
+                       * timer that a reset at `now` leaves at deadline == now: the same tick's timer step
+                       * fires it, so a follower with timeout 0 stands for election in the tick of every
+                       * heartbeat or vote that resets it, until a new role draws it a duration */
   int32_t* match;     /* Node.MatchIndex (main.go:29); NextIndex == MatchIndex+1 (main.go:280-281, 376-377) */
   uint8_t* fault;     /* per group, enum raft_fault */
   int32_t* log_term;  /* Log.Term (main.go:47) */

@@ -616,9 +616,10 @@ int raft_engine_create(const raft_config* cfg, raft_engine** out) {
   if (c.semantics != RAFT_SEM_REF && c.semantics != RAFT_SEM_RAFT)
     return fail(RAFT_EINVAL, "semantics must be RAFT_SEM_REF or RAFT_SEM_RAFT");
   if (c.tick_seconds < 1) return fail(RAFT_EINVAL, "tick_seconds must be >= 1");
+  // (the sums in 64 bits: min = 2^31-1, span = 1 wraps in int32 and would pass)
   if (c.follower_timeout_min < 1 || c.follower_timeout_span < 1 || c.candidate_timeout_min < 1 ||
-      c.candidate_timeout_span < 1 || c.follower_timeout_min + c.follower_timeout_span > 1024 ||
-      c.candidate_timeout_min + c.candidate_timeout_span > 1024)
+      c.candidate_timeout_span < 1 || int64_t(c.follower_timeout_min) + c.follower_timeout_span > 1024 ||
+      int64_t(c.candidate_timeout_min) + c.candidate_timeout_span > 1024)
     return fail(RAFT_EINVAL, "timer ranges must be >= 1 and below 1024 s (10-bit duration field)");
   if (c.isolate_per_65536 > 65536) return fail(RAFT_EINVAL, "isolate_per_65536 must be <= 65536");
   if (c.payload_crc > 1) return fail(RAFT_EINVAL, "payload_crc must be 0 or 1");
@@ -904,8 +905,8 @@ int raft_engine_features(const raft_engine* e, uint32_t* flags) {
 
 int raft_init_new_nodes(raft_engine* e, int64_t tick0) {
   if (!e) return fail(RAFT_EINVAL, "null engine");
+  if (int rc = check_ticks(e, tick0, 1)) return rc;   // (a refused call leaves the state as it is)
   state_replacing(e);
-  if (int rc = check_ticks(e, tick0, 1)) return rc;
   HIPCHK(hipSetDevice(e->cfg.device));
   HIPCHK(launch_init_new(e->R, e->P, make_trace(e, tick0), e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -915,8 +916,8 @@ int raft_init_new_nodes(raft_engine* e, int64_t tick0) {
 
 int raft_init_steady(raft_engine* e, int32_t leader, int64_t tick0) {
   if (!e) return fail(RAFT_EINVAL, "null engine");
+  if (int rc = check_ticks(e, tick0, 1)) return rc;   // (a refused call leaves the state as it is)
   state_replacing(e);
-  if (int rc = check_ticks(e, tick0, 1)) return rc;
   HIPCHK(hipSetDevice(e->cfg.device));
   HIPCHK(launch_init_steady(e->R, e->P, make_trace(e, tick0), leader, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -1175,10 +1176,10 @@ int raft_store_state_range(raft_engine* e, uint64_t first_group, uint64_t n_grou
 }
 
 int raft_load_state(raft_engine* e, const raft_state_view* v) {
-  if (e) state_replacing(e);
   if (!e || !v) return fail(RAFT_EINVAL, "null argument");
   if (!view_complete(v)) return fail(RAFT_EINVAL, "raft_load_state needs every field of the view");
-  if (int rc = check_rows(e, v, nullptr, e->cfg.groups)) return rc;
+  if (int rc = check_rows(e, v, nullptr, e->cfg.groups)) return rc;   // (a refused view leaves the state as it is)
+  state_replacing(e);
   if (int rc = scatter_view(e, 0, nullptr, e->cfg.groups, v)) return rc;
   state_replaced(e);
   return RAFT_OK;
@@ -2988,7 +2989,7 @@ int raft_checkpoint_save(raft_engine* e, const char* path) {
 }
 
 int raft_checkpoint_load(raft_engine* e, const char* path) {
-  if (e) state_replacing(e);
+  // (the state is replaced by raft_load_state at the end: a file that is refused leaves it as it is)
   if (!e || !path) return fail(RAFT_EINVAL, "null argument");
   const uint64_t G = e->cfg.groups, R = e->cfg.replicas, K = e->cfg.ring_depth;
   File f;

@@ -217,7 +217,8 @@ __global__ __launch_bounds__(256) void scatter_scalar_kernel(DevPlanes P, int ra
     const uint32_t x = rix<R>(g, r);
     const uint32_t role = in.role[k];
     const int32_t last = in.last[k], commit = in.commit[k], timeout = in.timeout[k];
-    if (r != primary && role != uint32_t(ROLE_F)) steady = false;
+    // (a follower with timeout 0 fires in the tick of the heartbeat that resets it: not a STEADY group)
+    if (r != primary && (role != uint32_t(ROLE_F) || timeout == 0)) steady = false;
     at(P.term, x) = in.term[k];
     at(P.last, x) = last;
     at(P.commit, x) = commit;

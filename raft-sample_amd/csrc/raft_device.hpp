@@ -933,14 +933,39 @@ struct Group {
     }
     // DEFER and MSYNC are consumed by the general path; the class flags are recomputed
     const uint32_t others = roles & ~(3u << (2 * (pri & 15)));
-    const bool led = pri < R && role(pri) == ROLE_L;
+    // (a follower with timer duration 0, which only a load can bring: a heartbeat resets its
+    // deadline to now and it fires in the same tick, so no fast-kernel class holds the group)
+    bool zero_dur = false;
+#pragma unroll
+    for (int r = 0; r < R; ++r) zero_dur |= role(r) == ROLE_F && dur[r] == 0;
+    const bool led = pri < R && role(pri) == ROLE_L && !zero_dur;
     const bool steady = led && others == 0u;
     // exactly one non-follower besides the primary: a candidate (ROLE_C = 1) ...
     const bool one = led && others != 0u && (others & (others - 1u)) == 0u;
     const bool onecand = one && (others & 0x5555u) != 0u;
     // ... or a leader (ROLE_L = 2) of a lower term (a stale leader still cut off)
     const int sx = one ? int(__builtin_ctz(others)) >> 1 : 0;
-    const bool onestale = SEM == SEM_RAFT && one && (others & 0xAAAAu) != 0u && sel(term, sx) < sel(term, pri & 7);
+    bool onestale = SEM == SEM_RAFT && one && (others & 0xAAAAu) != 0u && sel(term, sx) < sel(term, pri & 7);
+    if constexpr (SEM == SEM_RAFT) {
+      // ... whose commit rule is settled: the fast kernel lets a cut-off stale leader's CommitIndex
+      // stand, so the majority index its own growing log can reach, over its MatchIndex row as it
+      // stands (its row in xmatch), must not be above it. A loaded row may say otherwise (a
+      // MatchIndex past its own log, an uncommitted majority index): the general kernel keeps it.
+      if (onestale) {
+        int v[R];
+#pragma unroll
+        for (int p = 0; p < R; ++p) v[p] = p == sx ? I32MAX : at(prow(P.xmatch, sx * R + p, P.Gp), g);
+        int ninf = -1;
+#pragma unroll
+        for (int p = 0; p < R; ++p) {
+          int cnt = 0;
+#pragma unroll
+          for (int q = 0; q < R; ++q) cnt += v[q] >= v[p] ? 1 : 0;
+          if (cnt >= R / 2 + 1 && v[p] > ninf) ninf = v[p];
+        }
+        onestale = ninf <= sel(commit, sx);
+      }
+    }
     const int m = pri | (fault << 4) | (steady ? M_STEADY : 0) | (onecand ? M_ONECAND : 0) |
                   (onestale ? M_ONESTALE : 0) | (meta0 & M_DEFER);   // (DEFER: cleared by the window tail)
     if (m != meta0) at(P.gmeta, g) = uint16_t(m);
@@ -1414,6 +1439,7 @@ struct Group {
     for (; j < q.n; ++j) {
       const int idx = q.prev_idx + 1 + j;
       if (idx > l) break;
+      if (idx < 1) { raise(F_PANIC_GETLOG); return res; }   // (a request with prevLogIndex < 0: GetLog(0) panics)
       if (idx <= hw[Rp] - K) { raise(F_RING_EVICTED); return res; }
       int t; int64_t v; uint32_t c;
       src.fetch(j, t, v, c);

@@ -17,7 +17,8 @@ __device__ __forceinline__ int32_t scat_rs(uint32_t role, uint32_t voted, int ti
 // Timer start: the view's deadline is start + timeout (hb = HB_NONE never moves it)
 __device__ __forceinline__ int32_t scat_tstart(int deadline, int timeout) { return deadline - timeout; }
 // gmeta: primary (the lowest-id Leader, NO_PRIMARY without one) | fault << 4 |
-// STEADY when every other replica is a Follower. No other flag: DEFER, MSYNC,
+// STEADY when every other replica is a Follower with a timeout above 0 (one
+// of 0 fires in the tick of the heartbeat that resets it). No other flag: DEFER, MSYNC,
 // SSYNC, VX and the one-exception forms are the tick kernels' to set.
 __device__ __forceinline__ uint16_t scat_meta(int primary, uint32_t fault, bool steady) {
   return uint16_t(uint32_t(primary) | (fault << 4) | (steady ? uint32_t(M_STEADY) : 0u));

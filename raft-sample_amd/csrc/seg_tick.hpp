@@ -216,13 +216,28 @@ struct Seg {
     }
     const uint32_t nonf = mask(act && role != ROLE_F);
     const uint32_t cands = mask(act && role == ROLE_C);
-    const bool led = pri < R && ((leaders >> pri) & 1u);
+    // (a follower with timer duration 0, which only a load can bring: a heartbeat resets its
+    // deadline to now and it fires in the same tick, so no fast-kernel class holds the group)
+    const bool led = pri < R && ((leaders >> pri) & 1u) && mask(act && role == ROLE_F && dur == 0) == 0u;
     const uint32_t others = nonf & ~(1u << (pri & 15));
     const bool steady = led && others == 0u;
     const bool one = led && others != 0u && (others & (others - 1u)) == 0u;
     const bool onecand = one && (others & cands) != 0u;
     const int sx = one ? first_of(others) : 0;
-    const bool onestale = SEM == SEM_RAFT && one && (others & leaders) != 0u && bc(term, sx) < bc(term, pri & 7);
+    bool onestale = SEM == SEM_RAFT && one && (others & leaders) != 0u && bc(term, sx) < bc(term, pri & 7);
+    if constexpr (SEM == SEM_RAFT) {
+      // ... whose commit rule is settled (Group::store): the majority index its own growing log can
+      // reach, over its MatchIndex row as it stands, is not above its CommitIndex
+      const int v = (onestale && act && me != sx) ? at(prow(P.xmatch, sx * R + me, P.Gp), g) : I32MAX;
+      int cnt = 0;
+#pragma unroll
+      for (int q = 0; q < R; ++q) cnt += bc(v, q) >= v ? 1 : 0;
+      const int cand = (act && cnt >= R / 2 + 1) ? v : -1;
+      int ninf = -1;
+#pragma unroll
+      for (int q = 0; q < R; ++q) ninf = max(ninf, bc(cand, q));
+      onestale = onestale && ninf <= bc(commit, sx);
+    }
     // (DEFER stays until the window tail: the general kernel may run beside the
     // next tick's fast kernels, which must keep leaving this group alone)
     const int m = pri | (fault << 4) | (steady ? M_STEADY : 0) | (onecand ? M_ONECAND : 0) |

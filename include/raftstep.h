@@ -654,6 +654,118 @@ typedef struct raft_audit_info {  /* 88 B */
 int raft_group_audit(raft_engine* e, uint32_t checks, uint64_t first_group, raft_audit_hit* out, uint64_t cap,
                      raft_audit_info* info);
 
+/* ---- applied state --------------------------------------------------------
+ * The last step of the client loop, on the device: every committed entry is
+ * applied (folded) where the logs sit, and the replicas of a group are
+ * compared wherever their applied prefixes meet: state-machine safety, checked
+ * as the entries commit, with no entry leaving the device. The device keeps
+ * one 32-B record per fed (group, replica of the mask) from raft_apply_open to
+ * raft_apply_close / raft_engine_destroy (counted by raft_engine_info while
+ * open); an engine that never opens one allocates nothing for it.
+ *
+ * The chain. All arithmetic is 64-bit and wrapping; sm is the splitmix64 step
+ * of the trace RNG and the digest (x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30)
+ * * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31);
+ * gid = config.group_base + local group.
+ *   seed(gid, base) = sm(sm(gid) ^ uint64(uint32(base)))
+ *   folding entry i with Term T and Value V:
+ *     chain' = sm(sm(chain ^ (uint64(uint32(T)) << 32 | uint32(i))) ^ uint64(V))
+ *     sum'   = sum + V
+ * Stamps are not folded: entry equality is the audit's, Term and Value.
+ *
+ * raft_apply_step treats one fed pair with applied = c, CommitIndex cm,
+ * LastApplied l and high-water mark h (REF: h = l; ring depth K) by the commit
+ * feed's rule for a cursor c:
+ *   hi = min(cm, l)
+ *   hi < c:  the pair is counted in `stalled` and left alone (applied, base,
+ *            chain, sum, gaps); its trajectory is {c: chain}.
+ *   else     lo = min(max(c, h - K), hi).
+ *            lo > c: the lo - c entries that have left the ring are counted in
+ *              `lost`, the pair in `gapped`; gaps += 1 (saturating at 65535),
+ *              base = lo, chain = seed(gid, lo), sum = 0 (a re-seed).
+ *            Entries lo+1 .. hi are then folded in order (`folded` counts
+ *            them) and applied = hi: at most K entries per pair and step.
+ *            The trajectory is the chain value at lo and the chain value after
+ *            each folded index: {lo, lo+1, .., hi}.
+ * Divergence, per group, from the trajectories of this step:
+ *   two fed replicas a != b are comparable when their `base` after this step
+ *   is equal (chains of replicas with different bases are never compared);
+ *   a comparable pair diverges at i when i is the smallest index present in
+ *   both trajectories with different chain values;
+ *   a replica whose div_index is 0 and that belongs to a diverging pair (a
+ *   stalled one included) gets div_index = the smallest such i over its pairs
+ *   and div_peer = the lowest-id peer that attains that smallest index. Both
+ *   are sticky: a later step never changes them.
+ *   info->diverged counts the groups in which some replica was newly marked.
+ * The same state and records give the same bytes. The step reads the state as
+ * raft_feed_poll does: no group leaves its shared form, the steady tick's
+ * forms and an open feed stay, frozen groups are read like any other. */
+typedef struct raft_apply_record {   /* 32 B; one per fed (group, replica) */
+  int32_t  applied;    /* entries 1..applied have been looked at; -1: replica outside the mask */
+  int32_t  base;       /* the chain and the sum cover base+1..applied */
+  uint64_t chain;
+  int64_t  sum;        /* wrapping sum of Log.Value over base+1..applied */
+  int32_t  div_index;  /* 0: never diverged; else the first index at which this replica's chain
+                          differed from a comparable replica's (sticky) */
+  uint16_t gaps;       /* re-seeds so far, saturating at 65535 */
+  uint8_t  div_peer;   /* that replica, 0xFF: none */
+  uint8_t  reserved;   /* 0 */
+} raft_apply_record;
+/* Where the records start. FROM_START: applied = base = 0. FROM_COMMIT:
+ * applied = base = min(CommitIndex, LastApplied) (only what commits from now
+ * on). In both chain = seed(gid, base), div_peer = 0xFF (none) and everything
+ * else is 0. FROM_RECORDS: the caller's array, [G][R] records read for the
+ * replicas of the mask only; every record read must have 0 <= base <= applied
+ * and reserved == 0, otherwise the call is RAFT_EINVAL, found before anything
+ * changes (an open apply stays open and unchanged); what raft_apply_read
+ * returned resumes exactly. */
+enum raft_apply_start { RAFT_APPLY_FROM_START = 0, RAFT_APPLY_FROM_COMMIT = 1, RAFT_APPLY_FROM_RECORDS = 2 };
+typedef struct raft_apply_info { uint64_t folded, lost, stalled, gapped, diverged, reserved[3]; } raft_apply_info; /* 64 B */
+enum raft_apply_select { RAFT_APPLY_DIVERGED = 1u, RAFT_APPLY_GAPPED = 2u };
+typedef struct raft_apply_hit {      /* 24 B */
+  uint64_t group; uint32_t local;
+  uint8_t a, b, flags, fault;        /* flags: the select bits this group matches (all of them, asked for or not) */
+  int32_t index; uint32_t gaps;      /* gaps: summed over the fed replicas */
+} raft_apply_hit;
+/* replica_mask: the feed's rules (RAFT_EINVAL when 0 or with bits at or above
+ * R); start: enum raft_apply_start (anything else, or FROM_RECORDS without
+ * records, is RAFT_EINVAL). Opening an open apply replaces it. */
+int raft_apply_open(raft_engine* e, uint32_t replica_mask, uint32_t start, const raft_apply_record* records);
+/* One step over every fed pair (the rules above); info may not be NULL
+ * (RAFT_EINVAL); info->reserved is 0. */
+int raft_apply_step(raft_engine* e, raft_apply_info* info);
+/* out[i * R + r] = the record of replica r of groups[i] (local ids, in any
+ * order, repeats allowed), i < n; replicas outside the mask read as all zero
+ * with applied = -1. groups == NULL means groups 0..n-1. An id >= G, or n > G
+ * with a NULL `groups`, is RAFT_ERANGE with nothing written. */
+int raft_apply_read(raft_engine* e, const uint64_t* groups, uint64_t n, raft_apply_record* out);
+/* Read-only; looks at the records and at the groups' fault codes only. A group
+ * in [first_group, G) is a hit when
+ *   select & RAFT_APPLY_DIVERGED and some fed replica has div_index != 0, or
+ *   select & RAFT_APPLY_GAPPED   and some fed replica has gaps != 0.
+ * Witness of a diverged group: a = the lowest-id fed replica with div_index !=
+ * 0, b = its div_peer, index = its div_index. Of a group that is gapped but
+ * not diverged: a = the lowest-id fed replica with gaps != 0, b = 0xFF, index
+ * = its base. fault: enum raft_fault. Hits come in ascending group order; cap,
+ * info->matched, written and next_group follow raft_group_scan's contract
+ * (cap = 0 only counts, out may then be NULL; next_group = the local id after
+ * the last hit written, G when nothing is left, first_group when nothing was
+ * written and hits are left). The same records give the same bytes.
+ * RAFT_EINVAL: select 0 or with unknown bits, cap > 0 without out;
+ * RAFT_ERANGE: first_group > G (first_group == G is an empty scan). */
+int raft_apply_scan(raft_engine* e, uint32_t select, uint64_t first_group, raft_apply_hit* out, uint64_t cap,
+                    raft_scan_info* info);
+/* Step, read and scan without an open apply are RAFT_EINVAL; close then does
+ * nothing. A poisoned engine answers
+ * RAFT_EINTERNAL. Handler batches, raft_tick and raft_propose leave the apply
+ * open; whatever replaces the state (raft_init_*, raft_load_state,
+ * raft_checkpoint_load) closes it, like the feed. raft_restart_groups and
+ * raft_load_groups keep it open and reset the fed records of the listed
+ * groups, to the FROM_START state after a restart and to the FROM_COMMIT state
+ * of the loaded rows after a load; the others do not move. No collective: each
+ * engine applies its own shard. */
+int raft_apply_close(raft_engine* e);
+
 /* ---- multi-GPU statistics (RCCL over xGMI) -------------------------------
  * Groups shard by id (config.group_base); the only collective is the sum of
  * tick statistics. raft_tick reduces per-tick records on the device (NSTAT

@@ -24,6 +24,7 @@
 
 #include "../../include/raftstep.h"
 #include "kernels.h"
+#include "apply_records.hpp"
 #include "propose_plan.hpp"
 
 using namespace raftstep;
@@ -313,6 +314,13 @@ struct raft_engine {
   // group audit (raft_group_audit; k_audit.hip): its scratch, 8 B per group, from the first audit to the
   // engine's end; an engine that never audits allocates nothing
   void* audit_rec = nullptr;
+  // Applied state (raft_apply_*; k_apply.hip). Open: apply_mask != 0. The records ([G][apply_nm] of 32 B), the
+  // step's five device accumulators (zero between steps) and their pinned copy live from open to close.
+  uint32_t apply_mask = 0, apply_nm = 0;
+  void* apply_rec = nullptr;
+  unsigned long long* apply_dtot = nullptr;
+  unsigned long long* apply_res = nullptr;   // pinned, coherent: folded, lost, stalled, gapped, diverged
+  uint64_t apply_bytes = 0;     // of the records (raft_engine_info while the apply is open)
   int nranks = 1, rank = 0;
   uint64_t allreduces = 0;      // ncclAllReduce calls issued (diagnostics)
   bool comm_side = false;       // a sum on comm_stream the engine stream has not waited for
@@ -456,11 +464,27 @@ void feed_release(raft_engine* e) {
   e->feed_bytes = 0;
 }
 
+// Applied state: frees what raft_apply_open allocated (no step is in flight:
+// each one ends with a synchronise).
+void apply_release(raft_engine* e) {
+  if (!e->apply_mask && !e->apply_rec && !e->apply_dtot && !e->apply_res) return;
+  (void)hipSetDevice(e->cfg.device);
+  if (e->apply_rec) (void)hipFree(e->apply_rec);
+  if (e->apply_dtot) (void)hipFree(e->apply_dtot);
+  if (e->apply_res) (void)hipHostFree(e->apply_res);
+  e->apply_rec = nullptr;
+  e->apply_dtot = e->apply_res = nullptr;
+  e->apply_mask = e->apply_nm = 0;
+  e->device_bytes -= e->apply_bytes;
+  e->apply_bytes = 0;
+}
+
 // A call that replaces the state starts by dropping the list-skip proof (the
 // conservative direction, whatever happens next) ...
 void state_replacing(raft_engine* e) {
   host_mutation(e);
   feed_release(e);      // (the cursors describe the old logs)
+  apply_release(e);     // (and so do the applied records)
   e->vx_live = false;   // (the state is being replaced: no suffix survives)
   e->sh_live = false;   // (nor a shared entry: every rotation is rewritten)
 }
@@ -875,6 +899,7 @@ int raft_engine_destroy(raft_engine* e) {
   if (e->list_stream) (void)hipStreamDestroy(e->list_stream);
   if (e->half_stream) (void)hipStreamDestroy(e->half_stream);
   feed_release(e);
+  apply_release(e);
   if (e->audit_rec) (void)hipFree(e->audit_rec);
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->hist) (void)hipFree(e->hist);
@@ -2659,6 +2684,8 @@ int raft_restart_groups(raft_engine* e, const uint64_t* groups, uint64_t n, int6
   HIPCHK(hipMemcpyAsync(d_ids, ids.data(), size_t(n) * 4, hipMemcpyHostToDevice, e->stream));
   HIPCHK(launch_restart(e->R, e->P, make_trace(e, tick0), d_ids, uint32_t(n), e->feed_mask ? e->feed_cur : nullptr,
                         e->feed_nm, e->stream));
+  if (e->apply_mask)   // the restarted groups' applied records: the FROM_START state
+    HIPCHK(launch_apply_reset(e->R, e->P, 0, d_ids, uint32_t(n), e->apply_mask, e->apply_nm, e->apply_rec, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return RAFT_OK;
 }
@@ -2685,7 +2712,15 @@ int raft_load_groups(raft_engine* e, const uint64_t* groups, uint64_t n, const r
   for (uint64_t i = 0; i < n; ++i) ids[i] = uint32_t(groups[i]);
   if (int rc = ring_flush(e)) return rc;
   host_mutation(e);
-  return scatter_view(e, 0, ids.data(), n, v);
+  if (int rc = scatter_view(e, 0, ids.data(), n, v)) return rc;
+  if (e->apply_mask) {   // the loaded groups' applied records: the FROM_COMMIT state of the loaded rows
+    if (int rc = ensure_stage(e, size_t(n) * 4)) return rc;
+    uint32_t* d_ids = static_cast<uint32_t*>(e->stage);
+    HIPCHK(hipMemcpyAsync(d_ids, ids.data(), size_t(n) * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_apply_reset(e->R, e->P, 1, d_ids, uint32_t(n), e->apply_mask, e->apply_nm, e->apply_rec, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  return RAFT_OK;
 }
 
 // ---- group audit -----------------------------------------------------------
@@ -2800,6 +2835,205 @@ int raft_group_audit(raft_engine* e, uint32_t checks, uint64_t first_group, raft
   info->written = n;
   info->next_group = next;
   for (int k = 0; k < 6; ++k) info->per_check[k] = res[8 + k];
+  return RAFT_OK;
+}
+
+// ---- applied state ---------------------------------------------------------
+// The step reads the state as raft_feed_poll does (settle_check, vx_flush,
+// shared entries from the shared ring itself); read and scan look at the
+// records (the scan at gmeta's fault field too) and flush nothing.
+int raft_apply_open(raft_engine* e, uint32_t replica_mask, uint32_t start, const raft_apply_record* records) {
+  static_assert(sizeof(raft_apply_record) == 32 && sizeof(HostApplyRecord) == 32 && sizeof(raft_apply_info) == 64 &&
+                sizeof(raft_apply_hit) == 24, "raft_apply_record is 32 B, the info 64 B, a hit 24 B");
+  if (!e) return fail(RAFT_EINVAL, "null engine");
+  const uint64_t G = e->cfg.groups, R = e->cfg.replicas;
+  if (!replica_mask || (replica_mask >> R))
+    return fail(RAFT_EINVAL, "replica_mask %#x: needs at least one of the %llu replicas and no other bit", replica_mask,
+                (unsigned long long)R);
+  if (start > RAFT_APPLY_FROM_RECORDS) return fail(RAFT_EINVAL, "start %u is no raft_apply_start", start);
+  if (start == RAFT_APPLY_FROM_RECORDS && !records) return fail(RAFT_EINVAL, "RAFT_APPLY_FROM_RECORDS needs records");
+  const uint32_t nm = uint32_t(__builtin_popcount(replica_mask));
+  std::vector<HostApplyRecord> h;
+  if (start == RAFT_APPLY_FROM_RECORDS) {
+    h.resize(G * nm);
+    const uint64_t bad = apply_records_pack(reinterpret_cast<const HostApplyRecord*>(records), G, uint32_t(R),
+                                            replica_mask, h.data());
+    if (bad != G * R)
+      return fail(RAFT_EINVAL, "record of group %llu replica %llu: needs 0 <= base <= applied and reserved == 0",
+                  (unsigned long long)(bad / R), (unsigned long long)(bad % R));
+  }
+  if (int rc = settle_check(e)) return rc;
+  if (start == RAFT_APPLY_FROM_COMMIT)
+    if (int rc = vx_flush(e)) return rc;
+  apply_release(e);
+  HIPCHK(hipSetDevice(e->cfg.device));
+  const size_t rb = size_t(G) * nm * sizeof(raft_apply_record);
+  hipError_t rc = hipMalloc(&e->apply_rec, rb);
+  if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&e->apply_dtot), 64);
+  if (rc == hipSuccess) rc = hipHostMalloc(reinterpret_cast<void**>(&e->apply_res), 64, hipHostMallocCoherent);
+  if (rc == hipSuccess) rc = hipMemsetAsync(e->apply_dtot, 0, 64, e->stream);
+  e->apply_mask = replica_mask;   // (open from here on: apply_release frees whatever was allocated)
+  e->apply_nm = nm;
+  if (rc == hipSuccess) {
+    e->apply_bytes = rb;
+    e->device_bytes += rb;
+    if (start == RAFT_APPLY_FROM_RECORDS)
+      rc = hipMemcpyAsync(e->apply_rec, h.data(), rb, hipMemcpyHostToDevice, e->stream);
+    else
+      rc = launch_apply_reset(e->R, e->P, start == RAFT_APPLY_FROM_COMMIT, nullptr, uint32_t(G), replica_mask, nm,
+                              e->apply_rec, e->stream);
+  }
+  if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);
+  if (rc != hipSuccess) {
+    apply_release(e);
+    return fail(rc == hipErrorOutOfMemory ? RAFT_ENOMEM : RAFT_EHIP, "raft_apply_open: %s", hipGetErrorString(rc));
+  }
+  return RAFT_OK;
+}
+
+int raft_apply_step(raft_engine* e, raft_apply_info* info) {
+  if (!e || !info) return fail(RAFT_EINVAL, "null argument");
+  if (!e->apply_mask) return fail(RAFT_EINVAL, "raft_apply_step: no apply is open (raft_apply_open)");
+  if (int rc = settle_check(e)) return rc;
+  if (int rc = vx_flush(e)) return rc;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  // RAFTSTEP_APPLY_TIME=1: one stderr line per step with the kernel's span between two HIP events
+  // (tools/apply_probe.py; the events cost their creation per call)
+  const char* at_env = getenv("RAFTSTEP_APPLY_TIME");
+  hipEvent_t tev[2] = {nullptr, nullptr};
+  struct EvGuard {
+    hipEvent_t* v;
+    ~EvGuard() {
+      for (int i = 0; i < 2; ++i)
+        if (v[i]) (void)hipEventDestroy(v[i]);
+    }
+  } ev_guard{tev};
+  if (at_env && atoi(at_env) > 0)
+    for (hipEvent_t& x : tev) HIPCHK(hipEventCreate(&x));
+  if (tev[0]) HIPCHK(hipEventRecord(tev[0], e->stream));
+  HIPCHK(launch_apply_step(e->R, e->P, e->cfg.semantics == RAFT_SEM_RAFT, e->apply_mask, e->apply_nm, e->apply_rec,
+                           e->apply_dtot, e->apply_res, e->stream));
+  if (tev[0]) HIPCHK(hipEventRecord(tev[1], e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  *info = raft_apply_info{};
+  info->folded = e->apply_res[0];
+  info->lost = e->apply_res[1];
+  info->stalled = e->apply_res[2];
+  info->gapped = e->apply_res[3];
+  info->diverged = e->apply_res[4];
+  if (tev[0]) {
+    float a = 0;
+    HIPCHK(hipEventElapsedTime(&a, tev[0], tev[1]));
+    fprintf(stderr, "raft_apply_step: folded %llu step_us %.1f\n", (unsigned long long)info->folded, a * 1e3);
+  }
+  return RAFT_OK;
+}
+
+int raft_apply_read(raft_engine* e, const uint64_t* groups, uint64_t n, raft_apply_record* out) {
+  if (!e || (n && !out)) return fail(RAFT_EINVAL, "null argument");
+  if (!e->apply_mask) return fail(RAFT_EINVAL, "raft_apply_read: no apply is open (raft_apply_open)");
+  const uint64_t G = e->cfg.groups, R = e->cfg.replicas;
+  if (!groups && n > G)
+    return fail(RAFT_ERANGE, "raft_apply_read: %llu groups, the engine has %llu", (unsigned long long)n,
+                (unsigned long long)G);
+  if (groups)
+    for (uint64_t i = 0; i < n; ++i)
+      if (groups[i] >= G)
+        return fail(RAFT_ERANGE, "raft_apply_read: element %llu: group %llu outside the engine's %llu",
+                    (unsigned long long)i, (unsigned long long)groups[i], (unsigned long long)G);
+  if (int rc = settle_check(e)) return rc;
+  if (!n) return RAFT_OK;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  // chunks of list positions bound the staging: the chunk's ids, then its records
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const uint64_t chunk = std::min<uint64_t>(n, uint64_t(1) << 18);
+  const size_t b_ids = groups ? al(size_t(chunk) * 4) : 0;
+  if (int rc = ensure_stage(e, b_ids + size_t(chunk) * R * sizeof(raft_apply_record))) return rc;
+  char* base = static_cast<char*>(e->stage);
+  uint32_t* d_ids = reinterpret_cast<uint32_t*>(base);
+  std::vector<uint32_t> ids(groups ? chunk : 0);
+  for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
+    const uint64_t nc = std::min<uint64_t>(chunk, n - c0);
+    if (groups) {
+      for (uint64_t i = 0; i < nc; ++i) ids[i] = uint32_t(groups[c0 + i]);
+      HIPCHK(hipMemcpyAsync(d_ids, ids.data(), size_t(nc) * 4, hipMemcpyHostToDevice, e->stream));
+    }
+    HIPCHK(launch_apply_read(e->R, e->apply_rec, groups ? d_ids : nullptr, uint32_t(c0), uint32_t(nc), e->apply_mask,
+                             e->apply_nm, base + b_ids, e->stream));
+    HIPCHK(hipMemcpyAsync(out + c0 * R, base + b_ids, size_t(nc) * R * sizeof(raft_apply_record), hipMemcpyDeviceToHost,
+                          e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (ids is rewritten by the next chunk)
+  }
+  return RAFT_OK;
+}
+
+// The directory scan's route to the kernels: block sums, their scan, the
+// totals and the hits in raft_engine::stage.
+int raft_apply_scan(raft_engine* e, uint32_t select, uint64_t first_group, raft_apply_hit* out, uint64_t cap,
+                    raft_scan_info* info) {
+  if (!e || !info) return fail(RAFT_EINVAL, "null argument");
+  if (!select || (select & ~uint32_t(RAFT_APPLY_DIVERGED | RAFT_APPLY_GAPPED)))
+    return fail(RAFT_EINVAL, "raft_apply_scan: select %#x is no set of raft_apply_select bits", select);
+  if (cap && !out) return fail(RAFT_EINVAL, "raft_apply_scan: cap %llu without a buffer", (unsigned long long)cap);
+  if (!e->apply_mask) return fail(RAFT_EINVAL, "raft_apply_scan: no apply is open (raft_apply_open)");
+  const uint64_t G = e->cfg.groups;
+  if (first_group > G)
+    return fail(RAFT_ERANGE, "raft_apply_scan: first_group %llu past the engine's %llu groups",
+                (unsigned long long)first_group, (unsigned long long)G);
+  if (int rc = settle_check(e)) return rc;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  info->matched = info->written = 0;
+  info->next_group = G;
+  if (first_group == G) return RAFT_OK;
+  const uint32_t first = uint32_t(first_group);
+  const uint32_t nb = uint32_t((G + 255) / 256) - (first >> 8);
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t b_sum = al(size_t(nb) * 4), b_off = al(size_t(nb) * 8), b_tot = 256;
+  const size_t fixed = b_sum + b_off + b_tot;
+  unsigned long long res[4] = {0, 0, 0, 0};
+  // The hits' room is known only after the count; if the buffer then has to
+  // grow (ensure_stage frees the old one), count and scan run again in the new one.
+  uint64_t room = std::min<uint64_t>(cap, 1u << 16);
+  for (int pass = 0; pass < 2; ++pass) {
+    if (int rc = ensure_stage(e, fixed + size_t(room) * sizeof(raft_apply_hit))) return rc;
+    char* base = static_cast<char*>(e->stage);
+    uint32_t* bsum = reinterpret_cast<uint32_t*>(base);
+    uint64_t* boff = reinterpret_cast<uint64_t*>(base + b_sum);
+    // eight words: [0, 4) feed_scan_kernel's accumulators (unused here, zero), [4, 7) its results, [7] next_group
+    unsigned long long* tot = reinterpret_cast<unsigned long long*>(base + b_sum + b_off);
+    HIPCHK(hipMemsetAsync(tot, 0, 64, e->stream));
+    HIPCHK(launch_apply_count(e->R, e->P, e->apply_rec, e->apply_mask, e->apply_nm, select, first, bsum, e->stream));
+    HIPCHK(launch_feed_scan(bsum, boff, nb, tot, tot + 4, e->stream));
+    HIPCHK(hipMemcpyAsync(res, tot + 4, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));   // the total sizes the emit pass and the copy
+    const uint64_t n = std::min<uint64_t>(cap, res[0]);
+    if (n <= room) break;
+    room = n;
+  }
+  const uint64_t matched = res[0], n = std::min<uint64_t>(cap, matched);
+  uint64_t next = n == matched ? G : first_group;
+  if (n) {
+    char* base = static_cast<char*>(e->stage);
+    uint64_t* boff = reinterpret_cast<uint64_t*>(base + b_sum);
+    unsigned long long* d_next = reinterpret_cast<unsigned long long*>(base + b_sum + b_off) + 7;
+    void* hits = base + fixed;
+    unsigned long long h_next = 0;
+    HIPCHK(launch_apply_emit(e->R, e->P, e->apply_rec, e->apply_mask, e->apply_nm, select, first, boff, n, hits, d_next,
+                             e->stream));
+    HIPCHK(hipMemcpyAsync(out, hits, size_t(n) * sizeof(raft_apply_hit), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&h_next, d_next, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (n < matched) next = h_next;
+  }
+  info->matched = matched;
+  info->written = n;
+  info->next_group = next;
+  return RAFT_OK;
+}
+
+int raft_apply_close(raft_engine* e) {
+  if (!e) return fail(RAFT_EINVAL, "null engine");
+  apply_release(e);
   return RAFT_OK;
 }
 

@@ -16,7 +16,7 @@
 //        consecutive records) and stores the new cursors.
 // Order and cap come from the scan alone, so the same state and cursors give
 // the same bytes.
-#include "canon_view.hpp"
+#include "feed_range.hpp"
 
 namespace raftstep {
 
@@ -25,7 +25,8 @@ namespace {
 // The log-entry range of one group: per masked replica r the cursor c[r] as
 // read, lo[r] (the cursor moved past what left the ring) and n[r] entries
 // lo+1 .. lo+n to deliver; n = 0 and stalled for a pair whose cursor is ahead
-// of min(CommitIndex, LastApplied), all of the canonical view (canon_view.hpp).
+// of min(CommitIndex, LastApplied), all of the canonical view (canon_view.hpp);
+// the pair's arithmetic is feed_range.hpp's.
 template <int R>
 struct FeedRange {
   int c[R], lo[R], n[R];
@@ -47,15 +48,8 @@ __device__ __forceinline__ void feed_range(const DevPlanes& P, uint32_t g, int r
     const int hwm = cg.hwm(P, r, raft, l);
     const int c = cur[size_t(g) * nm + k];
     ++k;
-    const int hi = min(cm, l);
-    f.c[r] = f.lo[r] = c;
-    if (hi < c) {
-      ++f.stalled;
-      continue;
-    }
-    const int lo = min(max(c, hwm - int(P.K)), hi);
-    f.lo[r] = lo;
-    f.n[r] = hi - lo;
+    f.c[r] = c;
+    if (!feed_pair_range(c, cm, l, hwm, int(P.K), &f.lo[r], &f.n[r])) ++f.stalled;
   }
 }
 

@@ -296,6 +296,34 @@ hipError_t launch_audit_count(const DevPlanes& P, uint32_t first, const void* re
                               unsigned long long* tot, hipStream_t s);
 hipError_t launch_audit_emit(const DevPlanes& P, uint32_t first, const void* rec, const uint64_t* boff, uint64_t cap,
                              void* out, unsigned long long* next, hipStream_t s);
+// Applied state (k_apply.hip; raft_apply_*). rec: [G][nm] records of 32 B
+// (raft_apply_record), one per group and replica of `mask` (nm = its bits, in
+// replica order).
+// launch_apply_reset: the records of the groups ids[0..n) (ids null: groups
+// [0, n)) become the FROM_START state or, with from_commit, the FROM_COMMIT
+// state of the canonical view as it is.
+// launch_apply_step: one step over every group, then one wave that publishes
+// the totals; tot: 5 device words, zero between steps (the accumulators); res:
+// 5 words of pinned host memory = folded, lost, stalled, gapped, diverged.
+// launch_apply_read: out[i R + r] (32 B each) = the record of replica r of
+// group ids[i] (ids null: first + i), i < n; applied = -1 and zeroes outside
+// the mask.
+// launch_apply_count / _emit: raft_apply_scan over the 256-group blocks from
+// the one holding `first` on, as the directory's scan: per block its hits
+// (bsum); hits [0, cap) of the ascending group order to `out` (24 B each,
+// raft_apply_hit), cap >= 1 and at most the total, *next = the local id after
+// hit cap - 1.
+hipError_t launch_apply_reset(int R, const DevPlanes& P, int from_commit, const uint32_t* ids, uint32_t n, uint32_t mask,
+                              uint32_t nm, void* rec, hipStream_t s);
+hipError_t launch_apply_step(int R, const DevPlanes& P, int raft, uint32_t mask, uint32_t nm, void* rec,
+                             unsigned long long* tot, unsigned long long* res, hipStream_t s);
+hipError_t launch_apply_read(int R, const void* rec, const uint32_t* ids, uint32_t first, uint32_t n, uint32_t mask,
+                             uint32_t nm, void* out, hipStream_t s);
+hipError_t launch_apply_count(int R, const DevPlanes& P, const void* rec, uint32_t mask, uint32_t nm, uint32_t select,
+                              uint32_t first, uint32_t* bsum, hipStream_t s);
+hipError_t launch_apply_emit(int R, const DevPlanes& P, const void* rec, uint32_t mask, uint32_t nm, uint32_t select,
+                             uint32_t first, const uint64_t* boff, uint64_t cap, void* out, unsigned long long* next,
+                             hipStream_t s);
 hipError_t launch_stream_probe(int R, const uint16_t* a, SsRec* b, const uint16_t* c, int32_t* d, int32_t* rt,
                                int64_t* rv, uint32_t n, uint32_t slot, uint32_t kslots, hipStream_t s,
                                uint32_t mode = 0);

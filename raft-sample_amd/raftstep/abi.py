@@ -234,6 +234,23 @@ class TicketInfo(C.Structure):
     _fields_ = [("per_state", C.c_uint64 * 8)]
 
 
+# applied state (raft_apply_record / raft_apply_info / raft_apply_hit; enums raft_apply_start, raft_apply_select)
+APPLY_RECORD = np.dtype([("applied", "<i4"), ("base", "<i4"), ("chain", "<u8"), ("sum", "<i8"), ("div_index", "<i4"),
+                         ("gaps", "<u2"), ("div_peer", "u1"), ("reserved", "u1")], align=True)
+APPLY_HIT = np.dtype([("group", "<u8"), ("local", "<u4"), ("a", "u1"), ("b", "u1"), ("flags", "u1"), ("fault", "u1"),
+                      ("index", "<i4"), ("gaps", "<u4")], align=True)
+APPLY_FROM_START, APPLY_FROM_COMMIT, APPLY_FROM_RECORDS = 0, 1, 2
+APPLY_START = {"start": APPLY_FROM_START, "commit": APPLY_FROM_COMMIT, "records": APPLY_FROM_RECORDS}
+APPLY_DIVERGED, APPLY_GAPPED = 1, 2
+APPLY_INFO_NAMES = ("folded", "lost", "stalled", "gapped", "diverged")
+
+
+class ApplyInfo(C.Structure):
+    _fields_ = [("folded", C.c_uint64), ("lost", C.c_uint64), ("stalled", C.c_uint64), ("gapped", C.c_uint64),
+                ("diverged", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+assert APPLY_RECORD.itemsize == 32 and APPLY_HIT.itemsize == 24 and C.sizeof(ApplyInfo) == 64
 assert PROPOSAL.itemsize == 16 and TICKET.itemsize == 32 and TICKET_RESULT.itemsize == 8 and C.sizeof(TicketInfo) == 64
 assert AUDIT_HIT.itemsize == 24 and C.sizeof(AuditInfo) == 88
 assert AE_REQ.itemsize == 64 and AE_RESP.itemsize == 24 and LOG_ENTRY.itemsize == 16
@@ -292,16 +309,23 @@ SIGNATURES = {
     "raft_group_audit": (C.c_int, [P, C.c_uint32, C.c_uint64, P, C.c_uint64, P]),
     "raft_propose": (C.c_int, [P, C.c_int64, P, C.c_uint64, P]),
     "raft_ticket_status": (C.c_int, [P, P, C.c_uint64, P, P]),
+    "raft_apply_open": (C.c_int, [P, C.c_uint32, C.c_uint32, P]),
+    "raft_apply_step": (C.c_int, [P, P]),
+    "raft_apply_read": (C.c_int, [P, P, C.c_uint64, P]),
+    "raft_apply_scan": (C.c_int, [P, C.c_uint32, C.c_uint64, P, C.c_uint64, P]),
+    "raft_apply_close": (C.c_int, [P]),
 }
 
 
 # measurement / diagnostics entry points added in round 5: an older build
 # loaded through RAFTSTEP_LIB (A/B runs) may lack them
-# (and the commit feed, the group directory, the group audit and the client proposals, added later still)
+# (and the commit feed, the group directory, the group audit, the client proposals and the applied state, added
+# later still)
 OPTIONAL = ("raft_debug_diag_mode", "raft_stream_probe", "raft_engine_features",
             "raft_feed_open", "raft_feed_poll", "raft_feed_cursors", "raft_feed_close",
             "raft_group_scan", "raft_store_groups", "raft_restart_groups", "raft_load_groups", "raft_group_audit",
-            "raft_propose", "raft_ticket_status")
+            "raft_propose", "raft_ticket_status",
+            "raft_apply_open", "raft_apply_step", "raft_apply_read", "raft_apply_scan", "raft_apply_close")
 FEATURE_SHARED_ENTRIES, FEATURE_VIRTUAL_SUFFIXES = 1, 2   # raft_engine_features (include/raftstep.h)
 PROBE_PLAIN_RING, PROBE_NT_RECORD, PROBE_NO_HEARTBEAT = 1, 2, 4   # raft_stream_probe flags
 

@@ -306,6 +306,76 @@ class Engine:
         _check(self.lib.raft_ticket_status(self.h, _ptr(tickets), len(tickets), _ptr(out), C.byref(info)))
         return out, {k: int(info.per_state[i]) for i, k in enumerate(abi.TICKET_STATE_NAMES)}
 
+    # -- applied state -------------------------------------------------
+    def _replica_mask(self, replicas):
+        R = self.cfg.replicas
+        if replicas is None:
+            return (1 << R) - 1
+        if isinstance(replicas, (int, np.integer)):
+            mask = int(replicas)
+        else:
+            mask = 0
+            for r in replicas:
+                if int(r) < 0:
+                    raise ValueError(f"replica {r}")
+                mask |= 1 << int(r)
+        if not 0 <= mask < 1 << 32:
+            raise ValueError(f"replica mask {mask:#x}")
+        return mask
+
+    def apply_open(self, replicas=None, start="commit", records=None):
+        """Open the applied state (raft_apply_open). replicas: an iterable of
+        replica ids or a bit mask, None = all. start: "start" (from index 0),
+        "commit" (only what commits from now on) or "records" (the [G][R]
+        APPLY_RECORD array given, e.g. what apply_read() returned)."""
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, dtype=abi.APPLY_RECORD)
+            if rec.shape != (self.cfg.groups, self.cfg.replicas):
+                raise ValueError(f"apply records: shape {rec.shape}, expected ({self.cfg.groups}, {self.cfg.replicas})")
+        st = abi.APPLY_START[start] if isinstance(start, str) else int(start)
+        _check(self.lib.raft_apply_open(self.h, self._replica_mask(replicas), st, _ptr(rec)))
+
+    def apply_step(self):
+        """Fold what has committed since the last step into the records and
+        compare the replicas of every group (raft_apply_step): a dict with
+        folded, lost, stalled, gapped, diverged."""
+        info = abi.ApplyInfo()
+        _check(self.lib.raft_apply_step(self.h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k in abi.APPLY_INFO_NAMES}
+
+    def apply_read(self, ids=None):
+        """The records of the listed groups (local ids, any order, repeats
+        allowed; None: all groups) as an APPLY_RECORD array [n][R]; replicas
+        outside the mask read applied = -1 (raft_apply_read)."""
+        R = self.cfg.replicas
+        if ids is None:
+            out = np.zeros((self.cfg.groups, R), abi.APPLY_RECORD)
+            _check(self.lib.raft_apply_read(self.h, None, self.cfg.groups, _ptr(out)))
+            return out
+        ids = self._ids(ids)
+        out = np.zeros((len(ids), R), abi.APPLY_RECORD)
+        if len(ids):
+            _check(self.lib.raft_apply_read(self.h, _ptr(ids), len(ids), _ptr(out)))
+        return out
+
+    def apply_scan(self, select, first_group=0, cap=None):
+        """Groups in [first_group, G) with a diverged and / or a gapped
+        replica (raft_apply_scan; select: abi.APPLY_DIVERGED | APPLY_GAPPED):
+        (APPLY_HIT array in ascending group order, info dict with matched,
+        written, next_group). cap=None counts first, then takes every hit."""
+        info = abi.ScanInfo()
+        if cap is None:
+            _check(self.lib.raft_apply_scan(self.h, int(select), int(first_group), None, 0, C.byref(info)))
+            cap = info.matched
+        out = np.zeros(int(cap), abi.APPLY_HIT)
+        _check(self.lib.raft_apply_scan(self.h, int(select), int(first_group), _ptr(out), int(cap), C.byref(info)))
+        d = {k: int(getattr(info, k)) for k, _ in abi.ScanInfo._fields_}
+        return out[:d["written"]], d
+
+    def apply_close(self):
+        _check(self.lib.raft_apply_close(self.h))
+
     # -- the fused tick ------------------------------------------------
     def tick(self, first_tick, nticks=1, stats=True):
         if stats:
